@@ -13,14 +13,21 @@ process, as a Go Mixer is, holding one engine per GPU, each evaluating its conti
 libmxp's own RCCL all-reduce (ncclCommInitAll communicators, one ncclAllReduce of hits[R] ++
 quota_delta[K] per step).  At N = 1 nothing is reduced (the counters are the totals).
 
-The default run also measures C4 (configs[3]: 10k Pilot-style route rules x 1M requests per GPU) as
-the "c4" block (--no-c4: skip), C5 (configs[4]: the C2 step + the memquota batch routed to key owners
-inside the group) as "c5" (--no-c5), and C3 (configs[2]: CIDR, case-insensitive string and regex
-lists, 100k entries x 1M lookups per GPU) as "c3" (--no-c3).  Each predicate block also carries a
-"fresh_batch" figure (a new batch uploaded from host memory and evaluated every step, PCIe-inclusive)
-and an "end_to_end" Resolve figure.
+A plain run does only what the headline needs: it generates the inputs, compiles and uploads, warms
+up, times the K steps and prints the line (metric, value, ms_per_step and the run's configuration).
+--dump-outputs DIR then writes what the last timed step computed (dump_outputs below), so that two
+builds can be compared output for output: the same arguments give the same seeded inputs.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rules R] [--requests N_PER_GPU]
+--full adds every other measurement.  Per block: the per-kernel pass and the roofline figures, a
+"fresh_batch" figure (a new batch uploaded from host memory and evaluated every step, PCIe-inclusive),
+an "end_to_end" Resolve figure and the CPU baseline.  The default workload also measures C4
+(configs[3]: 10k Pilot-style route rules x 1M requests per GPU) as the "c4" block (--no-c4: skip),
+C5 (configs[4]: the C2 step + the memquota batch routed to key owners inside the group) as "c5"
+(--no-c5), and C3 (configs[2]: CIDR, case-insensitive string and regex lists, 100k entries x 1M
+lookups per GPU) as "c3" (--no-c3).
+
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rules R] [--requests N_PER_GPU] [--dump-outputs DIR]
+    python bench.py --full [--no-c4] [--no-c5] [--no-c3] [--no-cpu-baseline] [--fresh-steps F] [--e2e-reps E]
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
     python bench.py --workload c4 | c5 | c3-ip | c3-str | c3-regex | c5-quota [--devices 0,0]
 
@@ -76,6 +83,13 @@ def parse(argv=None):
     p.add_argument("--warmup", type=int, default=5)
     p.add_argument("--rules", type=int, default=10000)
     p.add_argument("--requests", type=int, default=1 << 20, help="requests (C3: lookups) per GPU")
+    p.add_argument("--full", action="store_true",
+                   help="every measurement beside the headline's timed steps: per-kernel times and roofline, the "
+                        "fresh-batch and end-to-end blocks, CPU baselines and (default workload) the C4 / C5 / C3 "
+                        "blocks; without it the options that shape those blocks have no effect")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32 / float64; "
+                        "large outputs as a fixed seeded sample)")
     p.add_argument("--cpu-sample-seconds", type=float, default=12.0)
     p.add_argument("--cpu-threads", type=int, default=host_threads())
     p.add_argument("--list-cpu-seconds", type=float, default=4.0, help="CPU-baseline sample per C3 list kind")
@@ -97,7 +111,76 @@ def parse(argv=None):
                         "u32 ids and offsets, mxp_batch_upload2) or wide (mxp_bag_batch)")
     p.add_argument("--gen-procs", type=int, default=min(16, host_threads()),
                    help="processes generating the synthetic shards (before any GPU work)")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        p.error("--steps must be at least 1 and --warmup at least 0")
+    return args
+
+
+def headline_only(args):
+    """A run without --full: a copy of `args` with every block beside the timed steps switched off."""
+    a = argparse.Namespace(**vars(args))
+    a.no_c3 = a.no_c4 = a.no_c5 = a.no_cpu_baseline = True
+    a.fresh_steps = a.e2e_reps = 0
+    return a
+
+
+# ---------------------------------------------------------------------------------- --dump-outputs
+DUMP_LIMIT = 64 * 10**6  # bytes of all the arrays of one --dump-outputs
+DUMP_BITMAP_BYTES = 10 * 10**6  # a sampled bitmap (float64 words)
+DUMP_VECTOR = 1 << 20  # entries of a sampled per-request vector
+
+
+def sample_index(n, m, seed):
+    """m of the indices 0 .. n-1 in ascending order, a fixed seeded choice (all of them when n <= m)."""
+    import numpy as np
+    if n <= m:
+        return np.arange(n, dtype=np.int64)
+    return np.sort(np.random.default_rng(seed).choice(n, size=m, replace=False)).astype(np.int64)
+
+
+def dump_outputs(dirname, arrays):
+    """Write {name: array} as DIR/<name>.npy.  Integer outputs go out as float64, which holds them
+    exactly (u32 bitmap words, i32 codes, indices, counters far below 2**53); u8 flags as float32."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype.itemsize <= 2 else np.float64)
+        total += a.nbytes
+        if total > DUMP_LIMIT:
+            raise RuntimeError("--dump-outputs: more than %d bytes (at %s)" % (DUMP_LIMIT, name))
+        np.save(os.path.join(dirname, name + ".npy"), a)
+    progress("wrote %d arrays, %.1f MB, to %s" % (len(arrays), total / 1e6, dirname))
+
+
+def predicate_outputs(g, ns, compact, hits, quota=None, delta=None):
+    """What a caller of the predicate step holds after it: per member k its match bitmap (and error
+    bitmap, or the per-request error flags of a compact evaluation) from mxp_group_download, the
+    group's hit counters (they accumulate over every step since the rules were compiled, warm-up
+    included) and, with memquota, the per-key deltas and the last batch's granted amounts.  Bitmaps
+    are sampled by request (request_index_<k>: the columns kept), long vectors by entry."""
+    G = len(ns)
+    W = (len(hits) + 31) // 32
+    m = max(1, min(4096, DUMP_BITMAP_BYTES // (8 * W)) // G)
+    out = {"hits": hits}
+    for k, n in enumerate(ns):
+        match, err = g.download(k, n, err_bitmap=not compact)
+        idx = sample_index(n, m, 1000 + k)
+        out["request_index_%d" % k] = idx
+        out["match_words_%d" % k] = match[:, idx]
+        if compact:
+            fidx = sample_index(n, DUMP_VECTOR // G, 2000 + k)
+            out["error_flag_index_%d" % k] = fidx
+            out["error_flags_%d" % k] = err[fidx]
+        else:
+            out["error_words_%d" % k] = err[:, idx]
+    if quota is not None:
+        granted = quota[1].granted()
+        qidx = sample_index(len(granted), DUMP_VECTOR, 3000)
+        out.update(quota_delta=delta, quota_granted_index=qidx, quota_granted=granted[qidx])
+    return out
 
 
 def cpu_baseline(manifest, rules, batch, seconds, threads, chunk=256):
@@ -597,9 +680,69 @@ def predicate_bench(args, kind, devices, data, with_quota=False):
     value = N_all * R * args.steps / elapsed
     hits, delta = g.counters(QUOTA_KEYS if quota else 0)
     hits_total = int(hits.sum())
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, predicate_outputs(g, [b.n for b in shards], compact, hits, quota, delta))
+
+    out = {
+        "metric": metric,
+        "value": value,
+        "unit": "pairs/s",
+        "n_gpus": G,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic (seeded %s workload; requests resident in HBM)" % kind.upper(),
+        "config": {"workload": workload % (R, N),
+                   "rules": R, "requests_per_gpu": N, "parallelism": "request-sharded dp%d" % G},
+        "group": {"devices": list(devices), "reduce": ["none", "rccl", "host"][g.reduce_mode],
+                  "note": g.note or None, "process": "one process drives every GPU (mxp_group)"},
+        "eval_ms": step_kernel_ms,
+        "host_enqueue_ms_per_step": LAST_ENQUEUE_MS,
+        "pack_upload_s": t_pack,
+        "error_output": "per-request flags (compact)" if compact else "error bitmap",
+        "hits_total": hits_total,
+    }
+    if quota is not None:
+        out["quota"] = {"keys": QUOTA_KEYS, "requests": int(quota[1].n),
+                        "requests_per_gpu": [quota[1].requests(k) for k in range(G)],
+                        "quota_delta_abs_total": int(np.abs(delta).sum()),
+                        "collective": "one all-reduce of hits[R] ++ quota_delta[K] per step (mxp_group_reduce)"}
+    if args.full:
+        out.update(kernel_figures(args, g, gb, kind, compact, with_quota, R, N))
+    if args.fresh_steps > 0 and not with_quota:
+        progress("%s fresh batches" % kind)
+        out["fresh_batch"] = fresh_batch_block(g, [data.shards(kind, 1), data.shards(kind, 2)], args.fresh_steps, R,
+                                               args.wire)
+    if args.e2e_reps > 0 and not with_quota:
+        sets = [shards] + ([data.shards(kind, 1), data.shards(kind, 2)] if args.fresh_steps > 0 else [])
+        progress("%s end to end" % kind)
+        out["end_to_end"] = end_to_end(g, sets, R, args.e2e_reps, args.wire)
+    gb.free()
+    if quota is not None:
+        quota[1].free()
+    quota = None
+    g.close()
+    if not args.no_cpu_baseline and G == 1:
+        if kind == "c4":
+            sample = W.c4_workload(n_rules=args.rules, n_requests=1 << 14, seed=4)[2]
+            out["cpu_baseline"] = cpu_baseline(manifest, rules, sample, args.cpu_sample_seconds, args.cpu_threads,
+                                               chunk=64)
+        else:
+            sample = W.c2_workload(n_rules=args.rules, n_requests=min(N, 1 << 18), seed=2)[2]
+            out["cpu_baseline"] = cpu_baseline(manifest, rules, sample, args.cpu_sample_seconds, args.cpu_threads)
+    return out
+
+
+def kernel_figures(args, g, gb, kind, compact, with_quota, R, N):
+    """--full: the per-kernel pass of one predicate block and its roofline figures (result keys)."""
+    import numpy as np
 
     # per-kernel durations of member 0 (HIP events recorded by libmxp around each launch on its stream),
-    # in a separate pass so the timed region above carries no extra synchronisation
+    # in a separate pass so the timed region carries no extra synchronisation
     e0 = g.engine(0)
     e0.set_timing(True)
     per = []
@@ -630,29 +773,9 @@ def predicate_bench(args, kind, devices, data, with_quota=False):
     achieved = alg_bytes / (eval_ms * 1e-3) / 1e9
     traffic = measured_traffic(kind + ("q" if with_quota else ""), R, N)
 
-    out = {
-        "metric": metric,
-        "value": value,
-        "unit": "pairs/s",
-        "n_gpus": G,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": elapsed / args.steps * 1e3,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": "synthetic (seeded %s workload; requests resident in HBM)" % kind.upper(),
-        "config": {"workload": workload % (R, N),
-                   "rules": R, "requests_per_gpu": N, "parallelism": "request-sharded dp%d" % G},
-        "group": {"devices": list(devices), "reduce": ["none", "rccl", "host"][g.reduce_mode],
-                  "note": g.note or None, "process": "one process drives every GPU (mxp_group)"},
-        "eval_ms": step_kernel_ms,
-        "host_enqueue_ms_per_step": LAST_ENQUEUE_MS,
+    return {
         "kernels_ms": {labels[0]: k_eval, labels[1]: k_index},
         "deferred_pairs": deferred,
-        "pack_upload_s": t_pack,
-        "error_output": "per-request flags (compact)" if compact else "error bitmap",
         "lds_bank_conflicts": lds_conflicts(kind),
         "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
@@ -664,35 +787,7 @@ def predicate_bench(args, kind, devices, data, with_quota=False):
                                 "kernels (the groups each serves) + mxp_index_kernel (+ mxp_inject_kernel with dense "
                                 "rules); traffic also counts mxp_hits_kernel when the hit counters are not fused"),
                      "alg_bytes_per_launch": alg_bytes, "alg_bytes_per_pair": alg_bytes / (N * R)},
-        "hits_total": hits_total,
     }
-    if quota is not None:
-        out["quota"] = {"keys": QUOTA_KEYS, "requests": int(quota[1].n),
-                        "requests_per_gpu": [quota[1].requests(k) for k in range(G)],
-                        "quota_delta_abs_total": int(np.abs(delta).sum()),
-                        "collective": "one all-reduce of hits[R] ++ quota_delta[K] per step (mxp_group_reduce)"}
-    if args.fresh_steps > 0 and not with_quota:
-        progress("%s fresh batches" % kind)
-        out["fresh_batch"] = fresh_batch_block(g, [data.shards(kind, 1), data.shards(kind, 2)], args.fresh_steps, R,
-                                               args.wire)
-    if args.e2e_reps > 0 and not with_quota:
-        sets = [shards] + ([data.shards(kind, 1), data.shards(kind, 2)] if args.fresh_steps > 0 else [])
-        progress("%s end to end" % kind)
-        out["end_to_end"] = end_to_end(g, sets, R, args.e2e_reps, args.wire)
-    gb.free()
-    if quota is not None:
-        quota[1].free()
-    quota = None
-    g.close()
-    if not args.no_cpu_baseline and G == 1:
-        if kind == "c4":
-            sample = W.c4_workload(n_rules=args.rules, n_requests=1 << 14, seed=4)[2]
-            out["cpu_baseline"] = cpu_baseline(manifest, rules, sample, args.cpu_sample_seconds, args.cpu_threads,
-                                               chunk=64)
-        else:
-            sample = W.c2_workload(n_rules=args.rules, n_requests=min(N, 1 << 18), seed=2)[2]
-            out["cpu_baseline"] = cpu_baseline(manifest, rules, sample, args.cpu_sample_seconds, args.cpu_threads)
-    return out
 
 
 def list_bench(args, devices, data, kind=None, emit=True):
@@ -735,6 +830,13 @@ def list_bench(args, devices, data, kind=None, emit=True):
             e1.record(s0)
     elapsed, ev_ms = timed_loop(step, args.steps, args.warmup, 1, None, sync=g.sync)
     kernel_ms = float(np.mean(ev_ms))
+    if args.dump_outputs:  # every member's HandleListEntry status codes (sampled past DUMP_VECTOR lookups)
+        arrays = {}
+        for k, t in enumerate(d_codes):
+            idx = sample_index(ns[k], DUMP_VECTOR // G, 4000 + k)
+            arrays["lookup_index_%d" % k] = idx
+            arrays["codes_%d" % k] = t.cpu().numpy()[idx]
+        dump_outputs(args.dump_outputs, arrays)
     n, alg = ns[0], algs[0]
     achieved = alg / (kernel_ms * 1e-3) / 1e9
     # the kernel the step launches (lists.cpp mxp_list_check_device): CIDR lookups regrouped by
@@ -789,6 +891,11 @@ def quota_bench(args, devices):
         now[0] += 10**8
     elapsed, ev_ms = timed_loop(step, args.steps, args.warmup, 1, None, sync=g.sync)
     kernel_ms = float(np.mean(ev_ms))
+    if args.dump_outputs:  # the last step's granted amounts (sampled past DUMP_VECTOR) and the per-key deltas
+        granted = qb.granted()
+        idx = sample_index(len(granted), DUMP_VECTOR, 3000)
+        dump_outputs(args.dump_outputs, {"quota_delta": g.counters(QUOTA_KEYS)[1], "quota_granted_index": idx,
+                                         "quota_granted": granted[idx]})
     n0 = qb.requests(0)
     alg = n0 * (4 + 8 + 1 + 8)  # key, amount, best effort read; granted written
     achieved = alg / (kernel_ms * 1e-3) / 1e9
@@ -883,6 +990,8 @@ def run(args, devices):
     kind = "c4" if wl == "c4" else "c2"
     progress("%s block" % wl)
     out = predicate_bench(args, kind, devices, data, with_quota=wl == "c5")
+    args = argparse.Namespace(**vars(args))
+    args.dump_outputs = None  # (the outputs written are the headline block's)
     keys = ("metric", "value", "unit", "ms_per_step", "eval_ms", "kernels_ms", "deferred_pairs", "pack_upload_s",
             "fresh_batch", "end_to_end", "config", "group", "roofline", "lds_bank_conflicts", "quota", "cpu_baseline",
             "hits_total")
@@ -914,6 +1023,8 @@ def run(args, devices):
 
 def main():
     args = parse()
+    if not args.full:
+        args = headline_only(args)
     if os.environ.get("MXP_BENCH_WATCHDOG"):  # (debugging: every thread's Python stack every N s)
         import faulthandler
         faulthandler.dump_traceback_later(float(os.environ["MXP_BENCH_WATCHDOG"]), repeat=True, file=sys.stderr)

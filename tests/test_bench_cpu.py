@@ -7,6 +7,7 @@ import sys
 import time
 
 import numpy as np
+import pytest
 
 import bench
 from istio_amd import workloads as W
@@ -65,6 +66,37 @@ def test_group_step_one_reduce_per_step():
     steps = [c for c in g.calls if c != "sync"]
     assert steps == ["eval", "quota", "reduce"] * 5 and ev == []
     assert now[0] == 10**18 + 5 * 10**8  # the quota clock advances one tick per step
+
+
+def test_plain_run_switches_every_other_block_off():
+    """Without --full only the timed steps remain, whatever the block options say; --full keeps them."""
+    argv = ["--steps", "7", "--warmup", "2", "--fresh-steps", "4", "--e2e-reps", "2"]
+    plain = bench.headline_only(bench.parse(argv))
+    assert (plain.steps, plain.warmup) == (7, 2)
+    assert plain.no_c3 and plain.no_c4 and plain.no_c5 and plain.no_cpu_baseline
+    assert plain.fresh_steps == 0 and plain.e2e_reps == 0
+    full = bench.parse(argv + ["--full"])
+    assert full.full and not (full.no_c3 or full.no_c4 or full.no_c5 or full.no_cpu_baseline)
+    assert full.fresh_steps == 4 and full.e2e_reps == 2 and full.dump_outputs is None
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    idx = bench.sample_index(1000, 10, 7)
+    assert np.array_equal(idx, bench.sample_index(1000, 10, 7))  # the same sample on every run
+    assert len(set(idx.tolist())) == 10 and (np.diff(idx) > 0).all() and 0 <= idx[0] and idx[-1] < 1000
+    assert np.array_equal(bench.sample_index(5, 10, 7), np.arange(5))
+    words = np.array([[0xFFFFFFFF, 1], [0x80000000, 0]], dtype=np.uint32)
+    bench.dump_outputs(str(tmp_path / "d"), {"words": words, "flags": np.array([0, 1, 255], dtype=np.uint8),
+                                             "hits": np.array([2**40 + 1], dtype=np.uint64)})
+    got = {f[:-4]: np.load(str(tmp_path / "d" / f)) for f in os.listdir(str(tmp_path / "d"))}
+    assert sorted(got) == ["flags", "hits", "words"]
+    assert got["words"].dtype == np.float64 and np.array_equal(got["words"].astype(np.uint32), words)
+    assert got["flags"].dtype == np.float32 and got["flags"].tolist() == [0.0, 1.0, 255.0]
+    assert got["hits"].dtype == np.float64 and int(got["hits"][0]) == 2**40 + 1
+    assert bench.DUMP_LIMIT <= 64 * 10**6
+    with pytest.raises(RuntimeError, match="more than"):  # one byte past the limit is refused
+        bench.dump_outputs(str(tmp_path / "big"), {"a": np.zeros(bench.DUMP_LIMIT // 8, dtype=np.float64),
+                                                   "b": np.zeros(1, dtype=np.uint8)})
 
 
 def _launch_rank_main(rank, world, port, out_path):

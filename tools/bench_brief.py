@@ -9,7 +9,9 @@ def main(path):
         if not line.startswith("{"):
             continue
         d = json.loads(line)
-        print("C2 %.4f ms/step  %.4g pairs/s  frac %.3f" % (d["ms_per_step"], d["value"], d["roofline"]["frac"]))
+        # (roofline and the blocks below: a `bench.py --full` log; a plain run's line has the headline alone)
+        print("C2 %.4f ms/step  %.4g pairs/s  frac %.3f" % (d["ms_per_step"], d["value"],
+                                                           d.get("roofline", {}).get("frac", float("nan"))))
         for k, v in d.items():
             if isinstance(v, dict) and "ms_per_step" in v and k not in ("fresh_batch",):
                 print("%-6s %.4f ms/step kernel %s" % (k, v["ms_per_step"], v.get("kernel_ms")))
