@@ -26,6 +26,20 @@ namespace {
 
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }
 
+// The argument block read where it is used (guard-index kernels).  Every kernel here takes its
+// mxp_kargs first, so the block sits at the start of the kernarg segment; a field read through this
+// view is one scalar load (a scalar-cache hit after the first wave).  The empty asm hides where the
+// pointer came from: the compiler then loads a field where the code reads it -- it can neither load
+// the whole 840-byte block at kernel entry nor merge the reads of two views -- so a field is live
+// from its view to its last use there, not from entry to exit (the index kernels parked 170-215
+// such values in VGPR lanes and paid a v_readlane for every use in their loops).
+typedef __attribute__((address_space(4))) const mxp_kargs ckargs;
+__device__ __forceinline__ ckargs& kargs_view() {
+    ckargs* p = (ckargs*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(p));
+    return *p;
+}
+
 __device__ __forceinline__ uint32_t wave_max(uint32_t v) {
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) v = max(v, (uint32_t)__shfl_xor((int)v, off, 64));
@@ -43,7 +57,8 @@ struct StrRef {
     uint32_t n;
 };
 
-__device__ __forceinline__ StrRef str_of(const mxp_kargs& A, uint64_t id) {
+template <class KA>
+__device__ __forceinline__ StrRef str_of(const KA& A, uint64_t id) {
     const bool g = id < A.n_gstr;
     const uint64_t d = g ? A.gstr_off[id] : A.bstr_off[id - A.n_gstr];
     StrRef r;
@@ -93,7 +108,15 @@ __device__ bool strfn(uint32_t fn, StrRef s, StrRef p) {
     return s.n == p.n && bytes_eq(s.p, p.p, p.n);
 }
 
-__device__ __forceinline__ void log_err(const mxp_kargs& A, uint32_t req, uint32_t rule, uint32_t code, uint32_t aux) {
+// (the index kernels' view reads the record fields here, where an error is logged: a rare path)
+__device__ __forceinline__ const mxp_kargs& fresh(const mxp_kargs& A) { return A; }
+__device__ __forceinline__ ckargs& fresh(ckargs&) { return kargs_view(); }
+template <class T> struct is_kview { static constexpr bool value = false; };
+template <> struct is_kview<__attribute__((address_space(4))) mxp_kargs> { static constexpr bool value = true; };
+
+template <class KA>
+__device__ __forceinline__ void log_err(const KA& A_, uint32_t req, uint32_t rule, uint32_t code, uint32_t aux) {
+    const auto& A = fresh(A_);
     if (!A.errlog) return;
     // (errcount[3]: some record is a conversion error, whose text prints the caller's value -- the
     // host then collects the records at once instead of when a text is asked for)
@@ -115,8 +138,49 @@ __device__ __forceinline__ void log_err(const mxp_kargs& A, uint32_t req, uint32
 // disjoint lanes; aliases are distinct rules), so neither atomic needs its return value: no
 // round trip per true pair.
 // fused hit counters on for this evaluation (kargs.hits_gate: a uniform scalar load)
-__device__ __forceinline__ bool counting(const mxp_kargs& A) {
+template <class KA>
+__device__ __forceinline__ bool counting(const KA& A) {
     return A.hits && (!A.hits_gate || *A.hits_gate != 0u);
+}
+
+// What a true pair of the guard-index kernels reads from the argument block, loaded once per phase
+// (a round of process_slot, the end of run_pairs) and dead after it: the fields live in scalar
+// registers through that phase's loops only.  The deferred-pair launch (engine.cpp dtp_on) has a
+// match bitmap and no dense rules, so those instantiations carry neither test.
+struct PairSink {
+    uint32_t* dtp_ent;
+    uint32_t dtp_cap;
+    const uint32_t* alias_off;
+    const uint32_t* aliases;
+    uint32_t* out_match;
+    const uint8_t* dense_of;
+    uint64_t n;
+    bool count;  // fused hit counters, counted per pair here
+};
+template <bool kDtp>
+__device__ __forceinline__ PairSink pair_sink() {
+    ckargs& A = kargs_view();
+    PairSink S;
+    S.alias_off = A.alias_off;
+    S.aliases = A.aliases;
+    if constexpr (kDtp) {
+        S.dtp_ent = A.dtp_ent;
+        S.dtp_cap = A.dtp_cap;
+        S.out_match = nullptr;
+        S.dense_of = nullptr;
+        S.n = 0;
+        // counted per pair here, or where the pair is filed (kargs.dtp_part: mxp_dtp_sort_kernel's
+        // histogram, dtp_push past the wave list)
+        S.count = !A.dtp_part && counting(A);
+    } else {
+        S.dtp_ent = nullptr;
+        S.dtp_cap = 0;
+        S.out_match = A.out_match;
+        S.dense_of = A.dense_of;
+        S.n = A.n;
+        S.count = counting(A);
+    }
+    return S;
 }
 
 // Deferred pairs (kargs.dtp_ent): the index kernel runs before the value-class fill, so a true or
@@ -124,15 +188,15 @@ __device__ __forceinline__ bool counting(const mxp_kargs& A) {
 // pair of q is produced by that wave) and OR-ed in by the fill as it streams the words out.  Pairs
 // past a wave's dtp_cap go to the overflow list (OR-ed in after the fill by the gated index launch);
 // past that list's capacity a flag re-runs the index kernel with plain OR-s after the fill.
-// (g_dtpn and g_rerr below keep four waves' entries, 272 bytes, in the one-wave workgroups too:
-// set_true / set_error are shared with kernels that know no workgroup shape)
+// (g_dtpn and g_rerr below keep four waves' entries, 272 bytes, in the one-wave workgroups too)
 __shared__ uint32_t g_dtpn[4];  // entries per wave of the index kernel's workgroup
-__device__ __forceinline__ void dtp_push(const mxp_kargs& A, uint32_t rule, uint32_t req, uint32_t plane) {
+__device__ __forceinline__ void dtp_push(uint32_t* dtp_ent, uint32_t dtp_cap, uint32_t rule, uint32_t req, uint32_t plane) {
     const uint32_t slot = atomicAdd(&g_dtpn[threadIdx.x >> 6], 1u);
-    if (slot < A.dtp_cap) {
-        A.dtp_ent[(uint64_t)(req >> 6) * A.dtp_cap + slot] = rule | (plane << 23) | ((req & 63u) << 24);
+    if (slot < dtp_cap) {
+        dtp_ent[(uint64_t)(req >> 6) * dtp_cap + slot] = rule | (plane << 23) | ((req & 63u) << 24);
         return;  // (a true pair in a wave list is counted by mxp_dtp_sort_kernel)
     }
+    ckargs& A = kargs_view();  // (the overflow list's fields: read here, a rare path)
     // past the wave list (histogram counting): counted here, the sort kernel never sees it
     if (plane == 0u && A.dtp_part && counting(A))
         __hip_atomic_fetch_add(A.hits + rule, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -146,36 +210,34 @@ __device__ __forceinline__ void dtp_push(const mxp_kargs& A, uint32_t rule, uint
 }
 
 template <bool kDtp = false>
-__device__ __forceinline__ void set_true1(const mxp_kargs& A, uint32_t rule, uint32_t req) {
+__device__ __forceinline__ void set_true1(const PairSink& S, uint32_t rule, uint32_t req) {
     const uint32_t bit = 1u << (rule & 31u);
-    if (kDtp) {
-        dtp_push(A, rule, req, 0u);
-        // counted per pair here, or where the pair is filed (kargs.dtp_part: mxp_dtp_sort_kernel's
-        // histogram, dtp_push past the wave list)
-        if (!A.dtp_part && counting(A)) __hip_atomic_fetch_add(A.hits + rule, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    __hip_atomic_fetch_or(A.out_match + (uint64_t)(rule >> 5) * A.n + req, bit, __ATOMIC_RELAXED,
-                          __HIP_MEMORY_SCOPE_AGENT);
-    if (counting(A)) __hip_atomic_fetch_add(A.hits + rule, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if constexpr (kDtp)
+        dtp_push(S.dtp_ent, S.dtp_cap, rule, req, 0u);
+    else
+        __hip_atomic_fetch_or(S.out_match + (uint64_t)(rule >> 5) * S.n + req, bit, __ATOMIC_RELAXED,
+                              __HIP_MEMORY_SCOPE_AGENT);
+    if (S.count) __hip_atomic_fetch_add(kargs_view().hits + rule, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 // ... and the same for the rule's aliases (indexed duplicates of its program, kargs.alias_off)
 // returns the number of pairs set
 template <bool kDtp = false>
-__device__ __forceinline__ uint32_t set_true(const mxp_kargs& A, uint32_t rule, uint32_t req) {
-    if (!A.out_match) return 0;
-    set_true1<kDtp>(A, rule, req);
+__device__ __forceinline__ uint32_t set_true(const PairSink& S, uint32_t rule, uint32_t req) {
+    if constexpr (!kDtp)
+        if (!S.out_match) return 0;
+    set_true1<kDtp>(S, rule, req);
     uint32_t c = 1;
-    if (A.alias_off)
-        for (uint32_t j = A.alias_off[rule]; j < A.alias_off[rule + 1]; j++, c++) set_true1<kDtp>(A, A.aliases[j], req);
+    if (S.alias_off)
+        for (uint32_t j = S.alias_off[rule]; j < S.alias_off[rule + 1]; j++, c++) set_true1<kDtp>(S, S.aliases[j], req);
     return c;
 }
 
-// an error pair found by the guard-index kernel, with its aliases
+// an error pair found by the guard-index kernel, with its aliases (a rare path: its fields are read here)
 __shared__ uint8_t g_rerr[4][64];  // deferred-pair index kernel: its tile's request error flags (kargs.req_err_init)
 template <bool kDtp = false>
-__device__ __forceinline__ void set_error(const mxp_kargs& A, uint32_t rule, uint32_t req) {
+__device__ __forceinline__ void set_error(uint32_t rule, uint32_t req) {
+    ckargs& A = kargs_view();
     if (A.req_err) {
         if constexpr (kDtp) {
             if (A.req_err_init) g_rerr[threadIdx.x >> 6][req & 63u] = 1;  // (the wave's own tile)
@@ -186,9 +248,11 @@ __device__ __forceinline__ void set_error(const mxp_kargs& A, uint32_t rule, uin
     }
     if (!A.out_err) return;
     if (kDtp) {
-        dtp_push(A, rule, req, 1u);
+        uint32_t* const ent = A.dtp_ent;
+        const uint32_t cap = A.dtp_cap;
+        dtp_push(ent, cap, rule, req, 1u);
         if (A.alias_off)
-            for (uint32_t j = A.alias_off[rule]; j < A.alias_off[rule + 1]; j++) dtp_push(A, A.aliases[j], req, 1u);
+            for (uint32_t j = A.alias_off[rule]; j < A.alias_off[rule + 1]; j++) dtp_push(ent, cap, A.aliases[j], req, 1u);
         return;
     }
     atomicOr(A.out_err + (uint64_t)(rule >> 5) * A.n + req, 1u << (rule & 31u));
@@ -201,11 +265,13 @@ __device__ __forceinline__ void set_error(const mxp_kargs& A, uint32_t rule, uin
 
 // constant-address-space views: uniform loads through them become scalar s_load_dwordxN
 typedef __attribute__((address_space(4))) const uint32_t cuint32;
+typedef __attribute__((address_space(4))) const mxp_index cindex;
 
 // Referenced-attribute tracking (mxp_eval_refs): one record per attribute read the VM performs
 // (VM_RES / VM_TRES / VM_VCOL: slot = column; VM_LOOKUP[K]: the map key), appended with one atomic
 // per wavefront.  Records past refcap are counted, not stored (the host re-runs with more room).
-__device__ __forceinline__ void ref_rec(const mxp_kargs& A, bool on, uint32_t req, uint32_t rule, uint32_t slot,
+template <class KA>
+__device__ __forceinline__ void ref_rec(const KA& A, bool on, uint32_t req, uint32_t rule, uint32_t slot,
                                         uint32_t key) {
     const uint64_t m = __ballot(on);
     if (!m) return;
@@ -229,11 +295,18 @@ __device__ __forceinline__ void ref_rec(const mxp_kargs& A, bool on, uint32_t re
 // lookups, virtual columns or regexps (Plan::tmpl_lite) -- without those cases the index kernel
 // needs far fewer registers
 // kS: threads per workgroup, the register file's row stride (deduced from `regs`)
-template <bool kRefs, bool kNfa = kRefs, bool kLite = false, uint32_t kS = 256>
-__device__ uint32_t run_rule(const mxp_kargs& A, cuint32* P, uint32_t len, uint32_t pc0, bool live, uint32_t rule,
+template <bool kRefs, bool kNfa = kRefs, bool kLite = false, uint32_t kS = 256, class KA>
+__device__ uint32_t run_rule(const KA& A, cuint32* P, uint32_t len, uint32_t pc0, bool live, uint32_t rule,
                              uint32_t req, uint64_t (*regs)[kS], uint32_t tid, bool fan = false) {
 #define REG(i) regs[i][tid]
+    // the columns, read once per call; the guard-index kernels (argument-block view) run in predicate
+    // mode only: no Eval results
+    constexpr bool kIdx = is_kview<KA>::value;
     const uint64_t N = A.n;
+    const uint8_t* const kinds = A.kinds;
+    const uint64_t* const vals = A.vals;
+    uint64_t* out_vals = nullptr;
+    if constexpr (!kIdx) out_vals = A.out_vals;
     uint32_t wait = live ? pc0 : MXP_VM_DONE;
     uint32_t res = PC_FALSE;
     uint32_t ecode = ERR_NONE, eaux = 0;  // the lane's error (logged once, after the loop)
@@ -260,7 +333,7 @@ __device__ uint32_t run_rule(const mxp_kargs& A, cuint32* P, uint32_t len, uint3
     } while (0)
 #define FINISHV(code_)                                                              \
     do {                                                                            \
-        if (A.out_vals) A.out_vals[(uint64_t)req * A.n_rules + rule] = (code_);     \
+        if (out_vals) out_vals[(uint64_t)req * A.n_rules + rule] = (code_);     \
         FINISH(code_);                                                              \
     } while (0)
 
@@ -282,8 +355,8 @@ __device__ uint32_t run_rule(const mxp_kargs& A, cuint32* P, uint32_t len, uint3
             if constexpr (kRefs) ref_rec(A, live, req, rule, x, MXP_VM_DONE);
             if (live) {
                 const uint64_t at = (uint64_t)x * N + req;
-                const uint32_t k = A.kinds[at];
-                uint64_t v = A.vals[at];
+                const uint32_t k = kinds[at];
+                uint64_t v = vals[at];
                 bool ok;
                 switch (y) {
                 case W_S: ok = k == MXP_STRING; break;
@@ -308,8 +381,8 @@ __device__ uint32_t run_rule(const mxp_kargs& A, cuint32* P, uint32_t len, uint3
             if constexpr (kRefs) ref_rec(A, live, req, rule, x, MXP_VM_DONE);
             if (live) {
                 const uint64_t at = (uint64_t)x * N + req;
-                const uint32_t k = A.kinds[at];
-                if (k == VC_VALUE) REG(d) = A.vals[at];
+                const uint32_t k = kinds[at];
+                if (k == VC_VALUE) REG(d) = vals[at];
                 else if (k == VC_ABSENT) FAIL(ERR_LOOKUP, z);
                 else FAIL(PANIC_MAPTYPE, 0);
             }
@@ -359,10 +432,10 @@ __device__ uint32_t run_rule(const mxp_kargs& A, cuint32* P, uint32_t len, uint3
         case VM_RET:
             if (live) {
                 const uint64_t v = REG(a);
-                if (A.out_vals) A.out_vals[(uint64_t)req * A.n_rules + rule] = v;
+                if (out_vals) out_vals[(uint64_t)req * A.n_rules + rule] = v;
                 if (y == 1) {
                     FINISH((uint32_t)v != 0 ? PC_TRUE : PC_FALSE);
-                } else if (A.out_vals) {
+                } else if (out_vals) {
                     FINISH(PC_FALSE);  // Eval: a non-bool result is just a value
                 } else {
                     FAIL(PANIC_NOTBOOL, 0);  // EvalPredicate: Result.AsBool panics (result.go:42-52)
@@ -505,10 +578,13 @@ __device__ uint32_t run_rule(const mxp_kargs& A, cuint32* P, uint32_t len, uint3
 #undef FINISH
 #undef FINISHV
 #undef REG
-    if (ecode != ERR_NONE && A.errlog) {
-        log_err(A, req, rule, ecode, eaux);
-        if (fan && A.alias_off)
-            for (uint32_t j = A.alias_off[rule]; j < A.alias_off[rule + 1]; j++) log_err(A, req, A.aliases[j], ecode, eaux);
+    if (ecode != ERR_NONE) {
+        const auto& E = fresh(A);
+        if (E.errlog) {
+            log_err(E, req, rule, ecode, eaux);
+            if (fan && E.alias_off)
+                for (uint32_t j = E.alias_off[rule]; j < E.alias_off[rule + 1]; j++) log_err(E, req, E.aliases[j], ecode, eaux);
+        }
     }
     return res;
 }
@@ -2099,21 +2175,26 @@ struct PairQueue {
 // only set their bit in the request's mask (LDS) -- the wave writes the bits of the rule and all its
 // aliases once per bitmap word at the end (inject_dense); the rest OR their bits in at once.
 template <bool kDtp, uint32_t kW>
-__device__ __forceinline__ uint32_t pair_true(const mxp_kargs& A, PairQueue& Q, uint32_t rule, uint32_t req) {
-    if (A.dense_of) {
-        const uint32_t d = A.dense_of[rule];
-        if (d != 0xFFu) {
-            atomicOr((unsigned long long*)&g_cm<kW>[Q.wave][req - Q.base], 1ull << d);
-            return 0u;  // counted by mxp_inject_kernel
+__device__ __forceinline__ uint32_t pair_true(const PairSink& S, PairQueue& Q, uint32_t rule, uint32_t req) {
+    if constexpr (!kDtp)
+        if (S.dense_of) {
+            const uint32_t d = S.dense_of[rule];
+            if (d != 0xFFu) {
+                atomicOr((unsigned long long*)&g_cm<kW>[Q.wave][req - Q.base], 1ull << d);
+                return 0u;  // counted by mxp_inject_kernel
+            }
         }
-    }
-    return set_true<kDtp>(A, rule, req);
+    return set_true<kDtp>(S, rule, req);
 }
 
 // run entries [off, off + cnt) of the queue, cnt <= 64
+// (the argument block's fields are read here, per call: nothing of it is live across the probes)
 template <bool kRefs, bool kNfa, bool kDtp, bool kProf = false, bool kLite = false, uint32_t kS = 256>
-__device__ void run_pairs(const mxp_kargs& A, PairQueue& Q, uint32_t off, uint32_t cnt, uint64_t (*regs)[kS],
-                          uint32_t tid) {
+__device__ void run_pairs(PairQueue& Q, uint32_t off, uint32_t cnt, uint64_t (*regs)[kS], uint32_t tid) {
+    ckargs& A = kargs_view();
+    const mxp_tmpl* const tmpls = A.tmpls;
+    const uint64_t* const rconst = A.rconst;
+    cuint32* const prog = (cuint32*)A.prog;
     const uint64_t t0 = kProf ? (uint64_t)wall_clock64() : 0ull;
     const uint32_t lane = tid & 63u;
     wave_sync_lds();
@@ -2130,20 +2211,23 @@ __device__ void run_pairs(const mxp_kargs& A, PairQueue& Q, uint32_t off, uint32
     for (uint64_t bal = __ballot(pending); bal; bal = __ballot(pending)) {
         const uint32_t tt = __builtin_amdgcn_readlane(t, (uint32_t)__builtin_ctzll(bal));
         const bool mine = pending && t == tt;
-        const mxp_tmpl* T = A.tmpls + tt;
+        const mxp_tmpl* T = tmpls + tt;
         const uint32_t toff = uni(T->off), pc0 = uni(T->pc0), len_t = uni(T->len), nconst = uni(T->nconst),
                        creg0 = uni(T->creg0);
         if (mine)
-            for (uint32_t c = 0; c < nconst; c++) regs[creg0 + c][tid] = A.rconst[(uint64_t)rule * MXP_VM_MAXREG + c];
-        cuint32* P = ((cuint32*)A.prog) + ((uint64_t)toff - pc0) * 4u;
+            for (uint32_t c = 0; c < nconst; c++) regs[creg0 + c][tid] = rconst[(uint64_t)rule * MXP_VM_MAXREG + c];
+        cuint32* P = prog + ((uint64_t)toff - pc0) * 4u;
         const uint32_t code = run_rule<kRefs, kNfa, kLite>(A, P, len_t, pc0, mine, rule, req, regs, tid, true);
         if (mine) res = code;
         pending = pending && !mine;
         if (kProf) Q.p_passes++;
     }
     // results out after the VM loop (its registers are dead here)
-    if (res == PC_TRUE) Q.ntrue += pair_true<kDtp, kS / 64u>(A, Q, rule, req);
-    if (res >= PC_ERROR && res != MXP_VM_DONE) set_error<kDtp>(A, rule, req);
+    if (__ballot(res == PC_TRUE)) {
+        const PairSink S = pair_sink<kDtp>();
+        if (res == PC_TRUE) Q.ntrue += pair_true<kDtp, kS / 64u>(S, Q, rule, req);
+    }
+    if (res >= PC_ERROR && res != MXP_VM_DONE) set_error<kDtp>(rule, req);
     if (kProf) {
         Q.p_vm += (uint64_t)wall_clock64() - t0;
         Q.p_runs++;
@@ -2178,10 +2262,10 @@ static_assert(MXP_COOP_T * MXP_COOP_T >= MXP_IXQ, "owners per round must not out
 
 // template of posting `pe` for the request whose subject is `s` (see process_slot): a template index,
 // MXP_TMPL_DIRECT (a true pair) or MXP_TMPL_SKIP (a dead literal-key posting)
-__device__ __forceinline__ uint32_t posting_tmpl(const mxp_kargs& A, const uint32_t* __restrict__ tmpl_of, uint32_t pe,
+__device__ __forceinline__ uint32_t posting_tmpl(bool post_tmpl, const uint32_t* __restrict__ tmpl_of, uint32_t pe,
                                                  StrRef s, uint32_t L, uint32_t& rule) {
     rule = pe;
-    if (!A.post_tmpl) return tmpl_of[rule];
+    if (!post_tmpl) return tmpl_of[rule];
     rule = pe & 0x7FFFFFu;  // the template rides in the posting (kargs.postings)
     const uint32_t code = pe >> 23;
     return code == 511u ? MXP_TMPL_DIRECT : code == 510u ? tmpl_of[rule]
@@ -2191,22 +2275,28 @@ __device__ __forceinline__ uint32_t posting_tmpl(const mxp_kargs& A, const uint3
 }
 
 template <bool kRefs, bool kNfa, bool kDtp, bool kProf = false, bool kLite = false, uint32_t kS = 256>
-__device__ __forceinline__ void process_slot(const mxp_kargs& A, PairQueue& Q, uint32_t tbl, uint32_t start,
+__device__ __forceinline__ void process_slot(PairQueue& Q, uint32_t tbl, uint32_t start,
                                              uint32_t len, uint32_t req, bool final, uint64_t (*regs)[kS],
                                              uint32_t tid, StrRef s = StrRef{nullptr, 0}, uint32_t L = 0) {
     const uint32_t lane = tid & 63u;
-    const uint32_t* __restrict__ tmpl_of = tbl ? A.rule_tmpl2 : A.rule_tmpl;
     const uint64_t below = (1ull << lane) - 1ull;
     uint32_t j0 = 0;
     for (;;) {
         if (Q.n < 64u && __ballot(j0 < len)) {
+            // this round's fields of the argument block (dead before run_pairs)
+            ckargs& A = kargs_view();
+            const uint32_t* __restrict__ const tmpl_of = tbl ? A.rule_tmpl2 : A.rule_tmpl;
+            const uint32_t* __restrict__ const postings = A.postings;
+            const bool post_tmpl = A.post_tmpl != 0u;
+            const bool coop = !(A.flags & 16384u);
+            const PairSink S = pair_sink<kDtp>();
             const uint32_t want = j0 < len ? len - j0 : 0u, freeq = MXP_IXQ - Q.n;  // freeq > 192
             const uint32_t before = wave_incl_sum(want, lane) - want;
             uint32_t take = before >= freeq ? 0u : min(want, freeq - before);
             uint32_t pos = Q.n;
             // the long shares, one owner at a time, 64 postings per step (the literal-key codes see
             // the owner's subject: broadcast with its range)
-            const bool owner = take >= MXP_COOP_T && !(A.flags & 16384u);
+            const bool owner = take >= MXP_COOP_T && coop;
             for (uint64_t om = __ballot(owner); om; om &= om - 1ull) {
                 const uint32_t o = (uint32_t)__builtin_ctzll(om);
                 const uint32_t ofirst = __builtin_amdgcn_readlane(start + j0, o);
@@ -2219,9 +2309,9 @@ __device__ __forceinline__ void process_slot(const mxp_kargs& A, PairQueue& Q, u
                 for (uint32_t b = 0; b < otake; b += 64u) {
                     uint32_t rule = 0, t = MXP_TMPL_SKIP;
                     if (b + lane < otake) {
-                        t = posting_tmpl(A, tmpl_of, A.postings[ofirst + b + lane], os, L, rule);
+                        t = posting_tmpl(post_tmpl, tmpl_of, postings[ofirst + b + lane], os, L, rule);
                         if (t == MXP_TMPL_DIRECT) {
-                            Q.ntrue += pair_true<kDtp, kS / 64u>(A, Q, rule, oreq);
+                            Q.ntrue += pair_true<kDtp, kS / 64u>(S, Q, rule, oreq);
                             t = MXP_TMPL_SKIP;
                         }
                     }
@@ -2247,9 +2337,9 @@ __device__ __forceinline__ void process_slot(const mxp_kargs& A, PairQueue& Q, u
             for (uint32_t j = 0; j < tmax; j++) {
                 uint32_t rule = 0, t = MXP_TMPL_SKIP;
                 if (j < take) {
-                    t = posting_tmpl(A, tmpl_of, A.postings[start + j0 + j], s, L, rule);
+                    t = posting_tmpl(post_tmpl, tmpl_of, postings[start + j0 + j], s, L, rule);
                     if (t == MXP_TMPL_DIRECT) {
-                        Q.ntrue += pair_true<kDtp, kS / 64u>(A, Q, rule, req);
+                        Q.ntrue += pair_true<kDtp, kS / 64u>(S, Q, rule, req);
                         t = MXP_TMPL_SKIP;
                     }
                 }
@@ -2269,7 +2359,7 @@ __device__ __forceinline__ void process_slot(const mxp_kargs& A, PairQueue& Q, u
         const bool more = __ballot(j0 < len) != 0;
         if (Q.n >= 64u || (Q.n > 0u && (final || more))) {
             const uint32_t k = min(Q.n, 64u);
-            run_pairs<kRefs, kNfa, kDtp, kProf, kLite>(A, Q, Q.n - k, k, regs, tid);
+            run_pairs<kRefs, kNfa, kDtp, kProf, kLite>(Q, Q.n - k, k, regs, tid);
             Q.n -= k;
             continue;
         }
@@ -2278,12 +2368,12 @@ __device__ __forceinline__ void process_slot(const mxp_kargs& A, PairQueue& Q, u
 }
 
 // equality probe: postings of the entry whose key is v (len 0: none)
-__device__ __forceinline__ void eq_probe(const mxp_kargs& A, uint32_t hoff, uint32_t hmask, uint64_t v, uint32_t& start,
-                                         uint32_t& len) {
+__device__ __forceinline__ void eq_probe(const mxp_hent* __restrict__ hents, uint32_t hoff, uint32_t hmask, uint64_t v,
+                                         uint32_t& start, uint32_t& len) {
     const uint32_t lo = (uint32_t)v, hi = (uint32_t)(v >> 32);
     uint32_t fi = 0xFFFFFFFFu;
     for (uint32_t slot = mxp_hash64(v) & hmask;; slot = (slot + 1) & hmask) {
-        const mxp_hent E = A.hents[hoff + slot];
+        const mxp_hent E = hents[hoff + slot];
         if (E.len == 0) break;
         if (E.klo == lo && E.khi == hi) {
             fi = hoff + slot;
@@ -2291,8 +2381,8 @@ __device__ __forceinline__ void eq_probe(const mxp_kargs& A, uint32_t hoff, uint
         }
     }
     if (fi != 0xFFFFFFFFu) {
-        start = A.hents[fi].start;
-        len = A.hents[fi].len;
+        start = hents[fi].start;
+        len = hents[fi].len;
     }
 }
 
@@ -2342,7 +2432,8 @@ __device__ __forceinline__ bool head_eq(uint64_t w0, uint64_t w1, const uint8_t*
 constexpr uint32_t KC = MXP_PROBE_KC;
 
 // entry pair (E, K) at `at` against the key of length L: 1 match, 0 another key, -1 empty slot
-__device__ __forceinline__ int entry_check(const mxp_kargs& A, const mxp_hent& E, const mxp_hent& K, uint32_t tag,
+template <class KA>
+__device__ __forceinline__ int entry_check(const KA& A, const mxp_hent& E, const mxp_hent& K, uint32_t tag,
                                            bool comp, uint32_t vlo, uint32_t vhi, uint32_t L, StrRef s, uint32_t hw1,
                                            bool by_head) {
     if (E.len == 0) return -1;
@@ -2360,19 +2451,23 @@ __device__ __forceinline__ int entry_check(const mxp_kargs& A, const mxp_hent& E
         const uint64_t m2 = L > 16u ? (1ull << ((L - 16u) * 8u)) - 1ull : 0ull;
         return (((w0 ^ k0) & m0) == 0 && ((w1 ^ k1) & m1) == 0 && ((w2 ^ (uint64_t)K.len) & m2) == 0) ? 1 : 0;
     }
-    const StrRef k = str_of(A, E.klo);
+    const StrRef k = str_of(fresh(A), E.klo);  // (a key past the inline bytes: rare)
     return (k.n == L && (by_head ? head_eq((uint64_t)s.p, hw1, k.p, L) : bytes_eq_a(s.p, k.p, L))) ? 1 : 0;
 }
 
-__device__ __forceinline__ void probe_chunk(const mxp_kargs& A, PrefixHash& ph, StrRef s, uint32_t hw1, bool by_head,
+template <class KA>
+__device__ __forceinline__ void probe_chunk(const KA& A, PrefixHash& ph, StrRef s, uint32_t hw1, bool by_head,
                                             bool sok, bool comp, uint32_t vlo, uint32_t vhi, uint32_t pmask,
-                                            uint32_t poff, uint32_t boff, const uint32_t* Ls, uint32_t kc,
+                                            uint32_t poff, uint32_t boff, cuint32* Ls, uint32_t kc,
                                             uint32_t (&st)[KC], uint32_t (&ln)[KC]) {
+    // the tables, read once per chunk
+    const mxp_hent* __restrict__ const hents = A.hents;
+    const uint32_t* __restrict__ const hbits = A.hbits;
     uint32_t slot[KC], tag[KC], L[KC], bw[KC];
     bool act[KC];
 #pragma unroll
     for (uint32_t j = 0; j < KC; j++) {
-        L[j] = j < kc ? uni(Ls[j]) : 0u;
+        L[j] = j < kc ? Ls[j] : 0u;
         act[j] = j < kc && sok && L[j] <= s.n;
         slot[j] = 0u;
         tag[j] = 0u;
@@ -2383,14 +2478,14 @@ __device__ __forceinline__ void probe_chunk(const mxp_kargs& A, PrefixHash& ph, 
         }
     }
 #pragma unroll
-    for (uint32_t j = 0; j < KC; j++) bw[j] = act[j] && A.hbits ? A.hbits[boff + (slot[j] >> 5)] : ~0u;
+    for (uint32_t j = 0; j < KC; j++) bw[j] = act[j] && hbits ? hbits[boff + (slot[j] >> 5)] : ~0u;
     mxp_hent E[KC], K[KC];
 #pragma unroll
     for (uint32_t j = 0; j < KC; j++) {
         act[j] = act[j] && ((bw[j] >> (slot[j] & 31u)) & 1u);
         if (act[j]) {
-            E[j] = A.hents[poff + 2u * slot[j]];
-            K[j] = A.hents[poff + 2u * slot[j] + 1u];
+            E[j] = hents[poff + 2u * slot[j]];
+            K[j] = hents[poff + 2u * slot[j] + 1u];
         }
     }
     uint32_t fi[KC];
@@ -2401,12 +2496,12 @@ __device__ __forceinline__ void probe_chunk(const mxp_kargs& A, PrefixHash& ph, 
         int r = entry_check(A, E[j], K[j], tag[j], comp, vlo, vhi, L[j], s, hw1, by_head);
         // (another key in the slot: the rest of the linear probe, this length alone)
         for (uint32_t sl = (slot[j] + 1u) & pmask; r == 0; sl = (sl + 1u) & pmask) {
-            if (A.hbits && !((A.hbits[boff + (sl >> 5)] >> (sl & 31u)) & 1u)) {
+            if (hbits && !((hbits[boff + (sl >> 5)] >> (sl & 31u)) & 1u)) {
                 r = -1;
                 break;
             }
             slot[j] = sl;
-            r = entry_check(A, A.hents[poff + 2u * sl], A.hents[poff + 2u * sl + 1u], tag[j], comp, vlo, vhi, L[j], s,
+            r = entry_check(A, hents[poff + 2u * sl], hents[poff + 2u * sl + 1u], tag[j], comp, vlo, vhi, L[j], s,
                             hw1, by_head);
         }
         if (r == 1) fi[j] = poff + 2u * slot[j];
@@ -2416,8 +2511,8 @@ __device__ __forceinline__ void probe_chunk(const mxp_kargs& A, PrefixHash& ph, 
         st[j] = 0u;
         ln[j] = 0u;
         if (fi[j] != 0xFFFFFFFFu) {
-            st[j] = A.hents[fi[j]].start;
-            ln[j] = A.hents[fi[j]].len & 0xFFFFFFu;
+            st[j] = hents[fi[j]].start;
+            ln[j] = hents[fi[j]].len & 0xFFFFFFu;
         }
     }
 }
@@ -2440,14 +2535,20 @@ namespace {
 // kProf: the profiling instantiations (kargs.wave_t, MXP_WAVE_TIMES) -- the hot kernels carry no
 // timing code
 template <bool kRefs, bool kNfa = kRefs, bool kDtp = false, bool kProf = false, bool kLite = false, uint32_t kS = 256>
-__device__ __forceinline__ void index_body(const mxp_kargs& A, uint64_t (*regs)[kS]) {
+__device__ __forceinline__ void index_body(uint64_t (*regs)[kS]) {
+    // The argument block is read through views (kargs_view), one per phase: kernel entry, each
+    // index, each probe, each round of postings, each VM batch, the end.  What a phase reads is dead
+    // after it, so the loops keep only their own scalars in registers.
     constexpr uint32_t kW = kS / 64u;  // waves per workgroup
     // chunked prefix probes in the lite kernel only (same-box A/B, profiles/r5_s8_ab_probe_c{2,4}.log:
     // KC 2 at 5 waves/SIMD C4 0.697 -> 0.691 ms, C2 0.4005 -> 0.3983 ms; KC 4 slower)
     constexpr bool kChunk = kLite && KC > 1;
     // after the fill (kargs.dtp_gate): the deferred pairs' overflow list OR-ed in, then -- only when
     // that list filled -- every pair again
-    if (A.dtp_gate) {
+    // (the gated launch has no deferred-pair lists of its own: mxp_index_kernel runs it)
+    if constexpr (!kDtp) {
+      ckargs& A = kargs_view();
+      if (A.dtp_gate) {
         const uint32_t no = min(uni(A.dtp_ovf_n[0]), A.dtp_ovf_cap);
         for (uint32_t i = blockIdx.x * kS + threadIdx.x; i < no; i += gridDim.x * kS) {
             const uint32_t q = A.dtp_ovf[2ull * i], e = A.dtp_ovf[2ull * i + 1];
@@ -2457,36 +2558,55 @@ __device__ __forceinline__ void index_body(const mxp_kargs& A, uint64_t (*regs)[
         // a counted evaluation's gate for the next one: stream (no true-pair count was kept)
         if (A.gate_out && blockIdx.x == 0 && threadIdx.x == 0) *A.gate_out = 0u;
         if (uni(*A.dtp_gate) == 0u) return;
+      }
     }
     const uint32_t tid = threadIdx.x;
     const uint32_t wave = uni(tid >> 6);
-    const uint64_t N = A.n;
     const uint32_t tile = blockIdx.x * kW + wave;  // 64 requests per wave
     const uint64_t t_start = kProf ? (uint64_t)wall_clock64() : 0ull;
-    PairQueue Q{wave, 0u, 0u, A.q0 + tile * 64u, 0ull, 0u, 0u, 0u};
+    PairQueue Q{wave, 0u, 0u, 0u, 0ull, 0u, 0u, 0u};
+    bool valid;
+    {
+        ckargs& A = kargs_view();
+        Q.base = A.q0 + tile * 64u;
+        valid = Q.base + (tid & 63u) < A.q1;
+        bool dense = false;  // (the deferred-pair launch has no dense rules: engine.cpp dtp_on)
+        if constexpr (!kDtp) dense = A.dense_of != nullptr;
+        if (dense) g_cm<kW>[wave][tid & 63u] = 0ull;
+        if (kDtp && (tid & 63u) == 0) g_dtpn[wave] = 0u;
+        if constexpr (kDtp)
+            if (A.req_err_init) g_rerr[wave][tid & 63u] = 0;
+        if (dense || kDtp) wave_sync_lds();
+        if (kProf && (tid & 63u) == 0)
+            for (uint32_t i = 3; i < 8; i++) A.wave_t[8ull * tile + i] = 0ull;
+    }
     const uint32_t req = Q.base + (tid & 63u);
-    const bool valid = req < A.q1;
-    if (A.dense_of) g_cm<kW>[wave][tid & 63u] = 0ull;
-    if (kDtp && (tid & 63u) == 0) g_dtpn[wave] = 0u;
-    if constexpr (kDtp)
-        if (A.req_err_init) g_rerr[wave][tid & 63u] = 0;
-    if (A.dense_of || kDtp) wave_sync_lds();
     uint32_t nmark = 0;  // profiling (kargs.wave_t): slots done
-    if (kProf && (tid & 63u) == 0)
-        for (uint32_t i = 3; i < 8; i++) A.wave_t[8ull * tile + i] = 0ull;
     // x == n_idx: a last pass with no probes that drains the pair queue
-    for (uint32_t x = 0; x <= A.n_idx; x++) {
-        const bool final = x == A.n_idx;
-        const mxp_index* X = A.idx + (final ? 0u : x);
-        const uint32_t col = uni(X->col), okset = uni(X->okset), hmask = uni(X->hmask), hoff = uni(X->hoff),
-                       kind = uni(X->prefix), plen0 = uni(X->plen0), nplen = uni(X->nplen);
+    for (uint32_t x = 0;; x++) {
+        // this index's view: its fields in one round of scalar loads, the index's own (rule-set
+        // data, constant through the launch) in a second
+        ckargs& A = kargs_view();
+        const uint32_t n_idx = A.n_idx;
+        const uint64_t N = A.n;
+        const bool probes_only = (A.flags & 1024u) != 0u;
+        const uint8_t* const kinds = A.kinds;
+        const uint64_t* const vals = A.vals;
+        const uint4* const heads = A.heads;
+        cuint32* const plens = (cuint32*)A.plens;
+        cindex* const idx = (cindex*)A.idx;
+        if (x > n_idx) break;
+        const bool final = x == n_idx;
+        cindex* X = idx + (final ? 0u : x);
+        const uint32_t col = X->col, okset = X->okset, hmask = X->hmask, hoff = X->hoff, kind = X->prefix,
+                       plen0 = X->plen0, nplen = X->nplen;
         const bool comp = kind == MXP_IX_COMPOSITE;
         // kinds and values of both columns are loaded together (independent loads, one round trip)
         bool ok = false;
         uint64_t v = 0;
         if (valid && !final) {  // (the last pass only drains the queue)
-            const uint32_t k = A.kinds[(uint64_t)col * N + req];
-            const uint64_t vv = A.vals[(uint64_t)col * N + req];
+            const uint32_t k = kinds[(uint64_t)col * N + req];
+            const uint64_t vv = vals[(uint64_t)col * N + req];
             ok = ((okset >> k) & 1u) != 0;
             v = ok ? vv : 0ull;
         }
@@ -2497,27 +2617,27 @@ __device__ __forceinline__ void index_body(const mxp_kargs& A, uint64_t (*regs)[
         uint64_t sv = v;
         uint32_t pmask = hmask, poff = hoff;
         if (comp) {
-            const uint32_t col2 = uni(X->col2), okset2 = uni(X->okset2);
-            pmask = uni(X->hmask2);
-            poff = uni(X->hoff2);
+            const uint32_t col2 = X->col2, okset2 = X->okset2;
+            pmask = X->hmask2;
+            poff = X->hoff2;
             if (valid && !final) {
-                const uint32_t k = A.kinds[(uint64_t)col2 * N + req];
-                const uint64_t vv = A.vals[(uint64_t)col2 * N + req];
+                const uint32_t k = kinds[(uint64_t)col2 * N + req];
+                const uint64_t vv = vals[(uint64_t)col2 * N + req];
                 sok = ok && ((okset2 >> k) & 1u) != 0;
                 if (sok) sv = vv;
             }
         }
         // short keys (every key length <= 12) hash and verify from the string's head (kargs.heads):
         // one coalesced 16-byte load instead of the descriptor and the bytes (scattered, dependent)
-        const uint32_t lmax = (!final && kind != MXP_IX_EQ && nplen) ? uni(A.plens[plen0 + nplen - 1u]) : 0u;
-        const uint32_t hslot = uni(X->hslot), boff = uni(X->boff);
-        const bool by_head = A.heads && hslot != MXP_VM_DONE && lmax <= 12u;
+        const uint32_t lmax = (!final && kind != MXP_IX_EQ && nplen) ? plens[plen0 + nplen - 1u] : 0u;
+        const uint32_t hslot = X->hslot, boff = X->boff;
+        const bool by_head = heads && hslot != MXP_VM_DONE && lmax <= 12u;
         // (the head's first word rides in the string pointer's registers: one of the two is live)
         StrRef s{nullptr, 0};
         uint32_t hw1 = 0;
         if (sok) {
             if (by_head) {
-                const uint4 hd = A.heads[(uint64_t)hslot * N + req];
+                const uint4 hd = heads[(uint64_t)hslot * N + req];
                 s.p = (const uint8_t*)((uint64_t)hd.x | ((uint64_t)hd.y << 32));
                 hw1 = hd.z;
                 s.n = hd.w;
@@ -2536,14 +2656,17 @@ __device__ __forceinline__ void index_body(const mxp_kargs& A, uint64_t (*regs)[
             const bool eq_slot = kind == MXP_IX_EQ || (comp && p == 0);
             if (final) {
             } else if (eq_slot) {
-                if (ok && (!comp || !sok)) eq_probe(A, hoff, hmask, v, start, len);
+                if (ok && (!comp || !sok)) eq_probe(kargs_view().hents, hoff, hmask, v, start, len);
             } else {
                 const uint32_t pp = p - (comp ? 1u : 0u);  // (the prefix length's index)
                 if constexpr (kChunk) {
                 // KC lengths at a time (probe_chunk); this length's range from the chunk's registers
                 const uint32_t j = pp % KC;
-                if (j == 0u) probe_chunk(A, ph, s, hw1, by_head, sok, comp, vlo, vhi, pmask, poff, boff,
-                                         A.plens + plen0 + pp, min(KC, nplen - pp), cst, cln);
+                if (j == 0u) {
+                    ckargs& AP = kargs_view();  // this chunk's view
+                    probe_chunk(AP, ph, s, hw1, by_head, sok, comp, vlo, vhi, pmask, poff, boff,
+                                (cuint32*)AP.plens + plen0 + pp, min(KC, nplen - pp), cst, cln);
+                }
 #pragma unroll
                 for (uint32_t i = 0; i < KC; i++)
                     if (i == j) {  // (selects: no dynamically indexed registers)
@@ -2551,7 +2674,10 @@ __device__ __forceinline__ void index_body(const mxp_kargs& A, uint64_t (*regs)[
                         len = cln[i];
                     }
                 } else {
-                const uint32_t L = uni(A.plens[plen0 + pp]);
+                ckargs& AP = kargs_view();  // this probe's view
+                const mxp_hent* __restrict__ const hents = AP.hents;
+                const uint32_t* __restrict__ const hbits = AP.hbits;
+                const uint32_t L = ((cuint32*)AP.plens)[plen0 + pp];
                 // the probe yields the entry's index; its postings range is read after the loop (reading
                 // start / len from the loop's 16-byte entry value was miscompiled at -O3 by this
                 // ROCm 7.2 hipcc: lanes resumed with another entry's range)
@@ -2561,11 +2687,11 @@ __device__ __forceinline__ void index_body(const mxp_kargs& A, uint64_t (*regs)[
                     const uint32_t tag = (uint32_t)(hf >> 32);
                     for (uint32_t slot = (uint32_t)hf & pmask;; slot = (slot + 1) & pmask) {
                         // an empty slot, told by the occupancy bitmap (no entry-pair request)
-                        if (A.hbits && !((A.hbits[boff + (slot >> 5)] >> (slot & 31u)) & 1u)) break;
+                        if (hbits && !((hbits[boff + (slot >> 5)] >> (slot & 31u)) & 1u)) break;
                         // entry pairs (vm.h mxp_index): both halves in one 32-byte load pair
                         const uint32_t at = poff + 2u * slot;
-                        const mxp_hent E = A.hents[at];
-                        const mxp_hent K = A.hents[at + 1u];
+                        const mxp_hent E = hents[at];
+                        const mxp_hent K = hents[at + 1u];
                         if (E.len == 0) break;
                         if (E.khi != tag) continue;
                         if (comp && (K.klo != vlo || K.khi != vhi)) continue;
@@ -2586,7 +2712,7 @@ __device__ __forceinline__ void index_body(const mxp_kargs& A, uint64_t (*regs)[
                             }
                             continue;
                         }
-                        const StrRef k = str_of(A, E.klo);
+                        const StrRef k = str_of(kargs_view(), E.klo);  // (a key past the inline bytes: rare)
                         if (k.n == L && (by_head ? head_eq((uint64_t)s.p, hw1, k.p, L) : bytes_eq_a(s.p, k.p, L))) {
                             fi = at;
                             break;
@@ -2594,29 +2720,31 @@ __device__ __forceinline__ void index_body(const mxp_kargs& A, uint64_t (*regs)[
                     }
                 }
                 if (fi != 0xFFFFFFFFu) {
-                    start = A.hents[fi].start;
-                    len = A.hents[fi].len & 0xFFFFFFu;
+                    start = hents[fi].start;
+                    len = hents[fi].len & 0xFFFFFFu;
                 }
                 }
             }
-            if (A.flags & 1024u) {  // ablation: probes only (results invalid)
+            if (probes_only) {  // ablation: probes only (results invalid)
                 if (len) Q.ntrue += start & 1u;
                 continue;
             }
             if (final || __ballot(len != 0))
-                process_slot<kRefs, kNfa, kDtp, kProf, kLite>(A, Q, comp && p > 0 ? 1u : 0u, start, len, req, final, regs, tid,
+                process_slot<kRefs, kNfa, kDtp, kProf, kLite>(Q, comp && p > 0 ? 1u : 0u, start, len, req, final, regs, tid,
                                                               s, kind == MXP_IX_PREFIX && !eq_slot && !final
-                                                                     ? uni(A.plens[plen0 + p]) : 0u);
+                                                                     ? ((cuint32*)kargs_view().plens)[plen0 + p] : 0u);
             if (kProf && (tid & 63u) == 0 && (final || nmark < 4u)) {  // profiling: phase marks
-                A.wave_t[8ull * tile + 3u + (final ? 4u : nmark)] = (uint64_t)wall_clock64();
+                kargs_view().wave_t[8ull * tile + 3u + (final ? 4u : nmark)] = (uint64_t)wall_clock64();
                 nmark++;
             }
         }
     }
-    if (A.dense_of) {  // masks for mxp_inject_kernel
-        wave_sync_lds();
-        if (valid) A.dense_cm[req] = g_cm<kW>[wave][tid & 63u];
-    }
+    ckargs& A = kargs_view();  // the end's view
+    if constexpr (!kDtp)
+        if (A.dense_of) {  // masks for mxp_inject_kernel
+            wave_sync_lds();
+            if (valid) A.dense_cm[req] = g_cm<kW>[wave][tid & 63u];
+        }
     if (kDtp) {  // the tile's deferred-pair count for mxp_dtp_sort_kernel
         wave_sync_lds();
         if ((tid & 63u) == 0) A.dtp_n[Q.base >> 6] = min(g_dtpn[wave], A.dtp_cap);
@@ -2646,7 +2774,7 @@ __device__ __forceinline__ void index_body(const mxp_kargs& A, uint64_t (*regs)[
 // (profiles/r1_v17_ab_ix6_*.log)
 extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void mxp_index_kernel(mxp_kargs A) {
     __shared__ uint64_t regs[MXP_VM_MAXREG][256];
-    index_body<false>(A, regs);
+    index_body<false>(regs);
 }
 // deferred index pairs (kargs.dtp_ent): true / error pairs recorded for the value-class fill.  5
 // waves/SIMD (96 VGPRs, 20 bytes of scratch) against 6 (80 VGPRs, 56 bytes of spills, which the PMC
@@ -2654,38 +2782,38 @@ extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(
 // 0.522 ms, C4 1.512 / 1.536 -> 1.491 / 1.519 ms (4 waves: 0.522, 1.514; profiles/r3_v3_ab_ix_occupancy_*.log)
 extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void mxp_index_dtp_kernel(mxp_kargs A) {
     __shared__ uint64_t regs[MXP_VM_MAXREG][64];
-    index_body<false, false, true>(A, regs);
+    index_body<false, false, true>(regs);
 }
 // ... for lite continuation templates (kargs.tmpl_lite: no lookups, virtual columns or regexps)
 extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(MXP_LITE_WAVES))) void mxp_index_dtp_lite_kernel(mxp_kargs A) {
     __shared__ uint64_t regs[MXP_VM_MAXREG][64];
-    index_body<false, false, true, false, true>(A, regs);
+    index_body<false, false, true, false, true>(regs);
 }
 // profiling (MXP_WAVE_TIMES): the two hot instantiations with wave start / end / phase marks
 extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(6))) void mxp_index_prof_kernel(mxp_kargs A) {
     __shared__ uint64_t regs[MXP_VM_MAXREG][256];
-    index_body<false, false, false, true>(A, regs);
+    index_body<false, false, false, true>(regs);
 }
 extern "C" __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5))) void mxp_index_dtp_prof_kernel(mxp_kargs A) {
     __shared__ uint64_t regs[MXP_VM_MAXREG][64];
-    index_body<false, false, true, true>(A, regs);
+    index_body<false, false, true, true>(regs);
 }
 // MXP_DEBUG_FLAGS 8192: the same body at 5 waves/SIMD (no scratch) -- A/B ablation
 extern "C" __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(5))) void mxp_index5_kernel(mxp_kargs A) {
     __shared__ uint64_t regs[MXP_VM_MAXREG][256];
-    index_body<false>(A, regs);
+    index_body<false>(regs);
 }
 
 // mxp_index_kernel for rule sets / batches with bit-parallel NFA regexps (kargs.nfa)
 extern "C" __global__ __launch_bounds__(256) void mxp_index_nfa_kernel(mxp_kargs A) {
     __shared__ uint64_t regs[MXP_VM_MAXREG][256];
-    index_body<false, true>(A, regs);
+    index_body<false, true>(regs);
 }
 
 // mxp_index_kernel with referenced-attribute records (mxp_eval_refs)
 extern "C" __global__ __launch_bounds__(256) void mxp_index_refs_kernel(mxp_kargs A) {
     __shared__ uint64_t regs[MXP_VM_MAXREG][256];
-    index_body<true>(A, regs);
+    index_body<true>(regs);
 }
 
 // After mxp_index_kernel, when the rule set has dense canonical rules (kargs.dense_of): every bitmap
