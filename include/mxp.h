@@ -195,6 +195,26 @@ int mxp_resolve_batch(mxp_engine* eng, const mxp_bag_batch* batch, uint32_t vari
  * (rule sets of at most 65536 rules; MXP_ERR_ARG otherwise): half the bytes of the action lists
  * brought back.  sel_rules has room for sel_cap ids of that width. */
 #define MXP_RESOLVE_IDS_U16 1u
+/* flags MXP_RESOLVE_IDS_DELTA8 (mxp_resolve_batch_ex, mxp_resolve_uploaded, mxp_resolve_submit and
+ * the mxp_group_resolve_* family; the same limit of 65536 rules, and exclusive with
+ * MXP_RESOLVE_IDS_U16: both set is MXP_ERR_ARG) writes the action lists as a delta-coded byte stream:
+ * about one byte per id where a request's ids lie close together, for rule sets with long lists
+ * (with about one id per request it brings back no less than the u16 list and costs two more
+ * kernels).  sel_rules is then a uint8_t stream; sel_cap and every sel_off entry are in BYTES, and
+ * request q's code is sel_rules[sel_off[q] .. sel_off[q+1]) -- delimited by its byte range alone, no
+ * id count is returned.  Each request is coded by itself, with prev = -1; for each selected rule r,
+ * in resolution order:
+ *     d = r - prev - 1
+ *     0 <= d <= 254:  one byte d
+ *     otherwise:      0xFF, r & 0xFF, r >> 8   (the absolute id, little-endian: a gap above 254, or
+ *                     the backward step from the default namespace's rule range to a lower one)
+ *     prev = r
+ * The code is canonical (the escape only where one byte cannot express the step), so two encoders
+ * agree byte for byte.  A request whose status is not MXP_RESOLVE_OK has an empty range.
+ * MXP_ERR_NOMEM as above: status, err_rule and sel_off (bytes) complete, retry with sel_off[n] bytes.
+ * A group's stream is the concatenation of its members': byte-identical to one engine's.  Into
+ * pinned sel_rules the stream is enqueued with the other outputs, as the ids of the other formats. */
+#define MXP_RESOLVE_IDS_DELTA8 2u
 int mxp_resolve_batch_ex(mxp_engine* eng, const mxp_bag_batch* batch, uint32_t variety, uint32_t flags,
                          uint8_t* status, uint32_t* err_rule, uint64_t* sel_off, void* sel_rules, uint64_t sel_cap);
 /* mxp_resolve_batch_ex over a batch uploaded before (mxp_batch_upload / mxp_batch_upload_ex, e.g. with

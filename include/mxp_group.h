@@ -151,6 +151,9 @@ int mxp_group_sync(mxp_group* g);
  * err_rule[q] and its selected rules sel_rules[sel_off[q] .. sel_off[q + 1]) exactly as one engine
  * resolving the whole batch would return them; MXP_ERR_NOMEM when sel_cap is short, with status,
  * err_rule and sel_off complete.  Error texts: mxp_group_pair_error with the global request index.
+ * flags as mxp_resolve_batch_ex: with MXP_RESOLVE_IDS_DELTA8 sel_rules is the byte stream, sel_off
+ * and sel_cap count bytes, and the stream is the concatenation of the members' (each request is
+ * coded by itself): byte-identical to one engine's.
  * mxp_group_resolve_split: from one host batch, split as mxp_group_upload_split.
  */
 int mxp_group_resolve_batch(mxp_group* g, const mxp_bag_batch* const* shards, uint32_t n_shards, uint32_t variety,

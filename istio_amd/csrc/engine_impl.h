@@ -33,6 +33,16 @@
 // start (~20 us between back-to-back evaluations, profiles/r4_final kernel trace).
 static constexpr unsigned kOrderEvent = hipEventDisableTiming | hipEventDisableSystemFence;
 
+// the format of a Resolve's action lists (the flags of mxp_resolve_batch_ex and its kin)
+enum class ResIds : uint8_t { U32, U16, DELTA8 };
+// false: a flag nobody knows, or two formats at once
+inline bool resolve_ids_format(uint32_t flags, ResIds* f) {
+    if (flags & ~(uint32_t)(MXP_RESOLVE_IDS_U16 | MXP_RESOLVE_IDS_DELTA8)) return false;
+    if ((flags & MXP_RESOLVE_IDS_U16) && (flags & MXP_RESOLVE_IDS_DELTA8)) return false;
+    *f = (flags & MXP_RESOLVE_IDS_DELTA8) ? ResIds::DELTA8 : (flags & MXP_RESOLVE_IDS_U16) ? ResIds::U16 : ResIds::U32;
+    return true;
+}
+
 extern "C" hipError_t mxp_launch_eval(const mxp_kargs* args, uint32_t grid_x, uint32_t grid_y, int vm, hipStream_t s);
 extern "C" hipError_t mxp_launch_index(const mxp_kargs* args, uint32_t grid, hipStream_t s);
 extern "C" hipError_t mxp_launch_d2h_copy(void* dst, const void* src, uint64_t n, hipStream_t s);
@@ -639,6 +649,7 @@ struct mxp_engine : public mxp::LowerTables {
     }
     void* bounce[2] = {nullptr, nullptr};
     uint32_t* res_small = nullptr;  // pinned: a compact Resolve's error-record and pair-overflow counts
+                                    // ([0..5]), a delta8 Resolve's id count ([8..9], a uint64_t)
     // the resolver's per-word tables on the device (res_lo / _hi / _amask / _empty) are those of
     // configuration res_gen and this variety (res_tab_key = res_gen << 6 | variety): kept across calls
     uint64_t res_gen = 0, res_tab_key = ~0ull;
@@ -699,6 +710,8 @@ struct mxp_engine : public mxp::LowerTables {
     // first applicable erroring rule from the error records (sparse pairs scattered into res_err_in),
     // block sums of the device scan of the counts
     DevBuf res_flags, res_err_in, res_pairs, res_bsum, res_stash;
+    // MXP_RESOLVE_IDS_DELTA8 (delta8.hip): bytes per request, their block sums and scan, the stream
+    DevBuf res_bcount, res_bsum8, res_boff, res_d8;
     std::vector<uint32_t> res_best;       // [n] host scratch: best resolution rank per request (~0 none)
     // the namespace names of the configuration on the device (mxp_ns_kernel): open-addressing table
     // of content hashes, descriptors, bytes

@@ -955,8 +955,9 @@ static int group_resolve(mxp_group* g, mxp_gbatch* gb, const mxp_bag_batch* cons
         for (mxp_dbatch* db : gb->db) views.push_back(db && db->wide ? &db->wide->view : nullptr);
         shards = views.data();
     }
+    ResIds ids_unused;  // (the members read the flags themselves: checked here before any work)
     if (!g || !shards || n_shards != g->size() || !status || !err_rule || !sel_off || (sel_cap && !sel_rules) ||
-        (flags & ~(uint32_t)MXP_RESOLVE_IDS_U16) || (gb && gb->db.size() != n_shards))
+        !resolve_ids_format(flags, &ids_unused) || (gb && gb->db.size() != n_shards))
         return MXP_ERR_ARG;
     for (uint32_t k = 0; k < n_shards; k++)
         if (!shards[k] || (gb && gb->n[k] != shards[k]->n_requests)) return MXP_ERR_ARG;

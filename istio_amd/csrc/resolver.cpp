@@ -9,11 +9,14 @@
 #include <numeric>
 #include <string_view>
 
+#include "delta8_args.h"
 #include "engine_impl.h"
 #include "pack_args.h"
 #include "resolve_args.h"
 
 extern "C" hipError_t mxp_launch_resolve(const mxp_resolve_args* a, int write, hipStream_t s);
+extern "C" hipError_t mxp_launch_d8(const mxp_d8_args* a, int write, uint32_t group, hipStream_t s);
+extern "C" uint32_t mxp_d8_group(uint64_t mean);
 extern "C" hipError_t mxp_launch_ns(const mxp_ns_args* a, hipStream_t s);
 extern "C" hipError_t mxp_launch_resolve_scatter(const uint32_t* pairs, uint32_t m, uint32_t* err_in, hipStream_t s);
 extern "C" hipError_t mxp_launch_resolve_first_err(const mxp_resolve_args* a, const void* recs, uint32_t m, hipStream_t s);
@@ -204,7 +207,7 @@ struct mxp_resolve_job {
     mxp_engine* eng = nullptr;
     const mxp_bag_batch* batch = nullptr;
     uint32_t variety = 0;
-    bool ids16 = false;
+    ResIds ids = ResIds::U32;  // the action lists' format
     bool compact = false;
     uint32_t n = 0, W = 0;
     uint64_t* ref_off = nullptr;
@@ -238,7 +241,9 @@ int resolve_begin(mxp_resolve_job& J) {
     const uint32_t n = J.n = batch->n_requests;
     const uint32_t NR = (uint32_t)eng->rules.size();
     const uint32_t W = J.W = (NR + 31) / 32;
-    if (J.ids16 && NR > 65536u) return eng->fail(MXP_ERR_ARG, "u16 rule ids: more than 65536 rules");
+    if (J.ids != ResIds::U32 && NR > 65536u)
+        return eng->fail(MXP_ERR_ARG, J.ids == ResIds::U16 ? "u16 rule ids: more than 65536 rules"
+                                                            : "delta8 rule ids: more than 65536 rules");
     DevBuf& dm = eng->res_dm;  // (engine-owned scratch: no allocation per call once large enough)
     DevBuf& de = eng->res_de;
     hipError_t e;
@@ -333,7 +338,8 @@ int resolve_end(mxp_resolve_job& J, uint8_t* status, uint32_t* err_rule, uint64_
     mxp_engine* eng = J.eng;
     const mxp_bag_batch* batch = J.batch;
     const uint32_t variety = J.variety, n = J.n, W = J.W;
-    const bool ids16 = J.ids16, compact = J.compact;
+    // (delta8: the u16 list into engine scratch, coded from there)
+    const bool d8 = J.ids == ResIds::DELTA8, ids16 = J.ids != ResIds::U32, compact = J.compact;
     uint64_t* ref_off = J.ref_off;
     mxp_attr_ref* refs = J.refs;
     const uint64_t ref_cap = J.ref_cap;
@@ -476,10 +482,75 @@ int resolve_end(mxp_resolve_job& J, uint8_t* status, uint32_t* err_rule, uint64_
     // the write pass guarded by the capacity (it writes nothing past it) and a download sized on the
     // device by sel_off[n] -- one synchronisation for every output instead of two (the ids' count is
     // known on the host only after the first).  Otherwise, or when they do not fit, after it.
-    const size_t isz = ids16 ? 2 : 4;
+    const size_t isz = d8 ? 1 : ids16 ? 2 : 4;  // (of a unit of sel_off / sel_cap: delta8 counts bytes)
     const uint64_t early_cap = place ? J.first_cap : sel_cap;
-    void* const sel_hd = n && early_cap && !ref_off && early_cap * isz <= kEarlyIdsMax ? eng->host_dev_ptr(sel_rules) : nullptr;
-    if (sel_hd) {
+    // (delta8: a u16 scratch of early_cap entries beside the stream -- ids <= bytes, so it suffices
+    // whenever the stream fits; the encoder reads the list in 8-byte words: 16 bytes of slack)
+    void* const sel_hd = n && early_cap && !ref_off && early_cap * (d8 ? 3 : isz) <= kEarlyIdsMax
+                             ? eng->host_dev_ptr(sel_rules)
+                             : nullptr;
+    // delta8: the u16 list stays on the device (d_sel, id offsets d_off) and three encoder steps
+    // follow the write pass -- bytes per request (mxp_d8_count_kernel), their scan into byte offsets
+    // (the Resolve's scan kernels over a second argument block) and the stream (mxp_d8_write_kernel).
+    // The caller's sel_off receives the byte offsets.
+    DevBuf &d_boff = eng->res_boff, &d_d8 = eng->res_d8;
+    mxp_d8_args D;
+    mxp_resolve_args S;  // (the scan of the byte counts)
+    memset(&D, 0, sizeof D);
+    memset(&S, 0, sizeof S);
+    uint64_t* ids_total = nullptr;  // (pinned: the ids' count, with the first downloads)
+    if (d8) {
+        if ((e = eng->res_bcount.reserve((size_t)n * 4 + 4)) != hipSuccess) return eng->hipfail(e, "alloc byte counts");
+        if ((e = eng->res_bsum8.reserve((size_t)grid * 8 + 8)) != hipSuccess) return eng->hipfail(e, "alloc byte sums");
+        if ((e = d_boff.reserve(((size_t)n + 1) * 8)) != hipSuccess) return eng->hipfail(e, "alloc byte offsets");
+        if (!eng->res_small && (e = hipHostMalloc((void**)&eng->res_small, 64, hipHostMallocDefault)) != hipSuccess) {
+            eng->res_small = nullptr;
+            return eng->hipfail(e, "pinned counters");
+        }
+        ids_total = (uint64_t*)(eng->res_small + 8);
+        *ids_total = 0;
+        D.n = n;
+        D.id_off = d_off.as<uint64_t>();
+        D.bcount = eng->res_bcount.as<uint32_t>();
+        D.block_sum = eng->res_bsum8.as<uint64_t>();
+        D.boff = d_boff.as<uint64_t>();
+        S.n = n;
+        S.count = D.bcount;
+        S.block_sum = D.block_sum;
+        S.sel_off_out = d_boff.as<uint64_t>();
+    }
+    // the u16 list in d_sel coded: byte offsets (cap: guarded, nothing when the ids exceed it) ...
+    auto d8_offsets = [&](uint64_t cap, uint32_t group) -> int {
+        D.ids = d_sel.as<uint16_t>();
+        D.cap = cap;
+        if ((e = mxp_launch_d8(&D, 0, group, eng->stream)) != hipSuccess ||
+            (e = mxp_launch_resolve(&S, 2, eng->stream)) != hipSuccess)
+            return eng->hipfail(e, "launch delta8 count");
+        return MXP_OK;
+    };
+    // ... and the stream, into d_d8 (room for `room` bytes)
+    auto d8_stream = [&](uint64_t room, uint64_t cap, uint32_t group) -> int {
+        if ((e = d_d8.reserve(room)) != hipSuccess) return eng->hipfail(e, "alloc delta8 stream");
+        D.ids = d_sel.as<uint16_t>();
+        D.out = d_d8.as<uint8_t>();
+        D.cap = cap;
+        if ((e = mxp_launch_d8(&D, 1, group, eng->stream)) != hipSuccess) return eng->hipfail(e, "launch delta8 write");
+        return MXP_OK;
+    };
+    if (sel_hd && d8) {
+        // (the lanes per request from the capacity: the host does not know the ids' count yet, and a
+        // caller sizes the capacity by the lists it expects)
+        const uint32_t group = mxp_d8_group(early_cap / n);
+        if ((e = d_sel.reserve(early_cap * 2 + 16)) != hipSuccess) return eng->hipfail(e, "alloc sel");
+        A.sel_rules = d_sel.as<uint32_t>();
+        A.sel_cap_dev = early_cap;
+        if ((e = mxp_launch_resolve(&A, write_mode, eng->stream)) != hipSuccess) return eng->hipfail(e, "launch resolve write");
+        A.sel_cap_dev = 0;
+        if ((rc = d8_offsets(early_cap, group)) || (rc = d8_stream(early_cap, early_cap, group))) return rc;
+        if ((e = mxp_launch_d2h_copy_ids(sel_hd, d_d8.p, d_boff.as<uint64_t>() + n, 1u, early_cap, eng->stream)) !=
+            hipSuccess)
+            return eng->hipfail(e, "download sel");
+    } else if (sel_hd) {
         if ((e = d_sel.reserve(early_cap * isz)) != hipSuccess) return eng->hipfail(e, "alloc sel");
         A.sel_rules = d_sel.as<uint32_t>();
         A.sel_cap_dev = early_cap;
@@ -492,12 +563,14 @@ int resolve_end(mxp_resolve_job& J, uint8_t* status, uint32_t* err_rule, uint64_
     if (!n) {
         if (!place) sel_off[0] = 0;
     } else {
-        const std::vector<mxp_engine::Piece> outs = {{status, d_status.p, n},
-                                                     {err_rule, d_err_rule.p, (size_t)n * 4},
-                                                     // (a group member leaves sel_off[0] alone: that
-                                                     // entry is the previous member's last one)
-                                                     place ? mxp_engine::Piece{sel_off + 1, d_off.as<uint64_t>() + 1, (size_t)n * 8}
-                                                           : mxp_engine::Piece{sel_off, d_off.p, ((size_t)n + 1) * 8}};
+        // (delta8: the byte offsets, where the stream was enqueued above; else after the ids' count)
+        const uint64_t* const offs = d8 ? d_boff.as<uint64_t>() : d_off.as<uint64_t>();
+        std::vector<mxp_engine::Piece> outs = {{status, d_status.p, n}, {err_rule, d_err_rule.p, (size_t)n * 4}};
+        // (a group member leaves sel_off[0] alone: that entry is the previous member's last one)
+        if (!d8 || sel_hd)
+            outs.push_back(place ? mxp_engine::Piece{sel_off + 1, offs + 1, (size_t)n * 8}
+                                 : mxp_engine::Piece{sel_off, offs, ((size_t)n + 1) * 8});
+        if (d8) outs.push_back({ids_total, d_off.as<uint64_t>() + n, 8});
         if ((rc = eng->download_all(outs, "download resolve outputs"))) return rc;
     }
     eng->trace_mark("resolve kernels + downloads");
@@ -510,6 +583,23 @@ int resolve_end(mxp_resolve_job& J, uint8_t* status, uint32_t* err_rule, uint64_
         const mxp_engine::RefScope scope{&info, status, err_rule, variety};
         ref_rc = eng->refs_assemble(batch, recs, &scope, ref_off, refs, ref_cap);
         if (ref_rc && ref_rc != MXP_ERR_NOMEM) return ref_rc;
+    }
+    // delta8 after the first synchronisation: the ids' count is known.  Unless the guarded passes above
+    // ran with room for them (then the u16 list and the byte offsets stand), the u16 list is written
+    // now and its byte offsets computed and brought back.
+    const uint64_t ids_n = d8 && n ? *ids_total : 0;
+    const uint32_t d8_group = d8 && n ? mxp_d8_group((ids_n + n - 1) / n) : 1u;
+    if (d8 && n && !(sel_hd && ids_n <= early_cap)) {
+        if ((e = d_sel.reserve(ids_n * 2 + 16)) != hipSuccess) return eng->hipfail(e, "alloc sel");
+        A.sel_rules = d_sel.as<uint32_t>();
+        if (ids_n && (e = mxp_launch_resolve(&A, write_mode, eng->stream)) != hipSuccess)
+            return eng->hipfail(e, "launch resolve write");
+        if ((rc = d8_offsets(0, d8_group))) return rc;
+        if ((rc = eng->download_all({place ? mxp_engine::Piece{sel_off + 1, d_boff.as<uint64_t>() + 1, (size_t)n * 8}
+                                           : mxp_engine::Piece{sel_off, d_boff.p, ((size_t)n + 1) * 8}},
+                                    "download byte offsets")))
+            return rc;
+        eng->trace_mark("delta8: u16 list + byte offsets");
     }
     const uint64_t total = n ? sel_off[n] : 0;
     // (a group member learns where its ids go in the whole batch's list once every member knows its
@@ -525,7 +615,10 @@ int resolve_end(mxp_resolve_job& J, uint8_t* status, uint32_t* err_rule, uint64_
         eng->trace_mark("action lists (with the outputs)");
         return ref_rc;
     }
-    if (total) {
+    if (total && d8) {  // (the u16 list is in d_sel)
+        if ((rc = d8_stream(total, 0, d8_group))) return rc;
+        if ((rc = eng->download((uint8_t*)sel_rules + (size_t)at, d_d8.p, total, "download sel"))) return rc;
+    } else if (total) {
         if ((e = d_sel.reserve(total * isz)) != hipSuccess) return eng->hipfail(e, "alloc sel");
         A.sel_rules = d_sel.as<uint32_t>();
         if ((e = mxp_launch_resolve(&A, write_mode, eng->stream)) != hipSuccess) return eng->hipfail(e, "launch resolve write");
@@ -543,7 +636,7 @@ int resolve_end(mxp_resolve_job& J, uint8_t* status, uint32_t* err_rule, uint64_
 // device (mxp_ns_kernel on the batch as uploaded); each failing request's first applicable error is
 // found from the records on the host and scattered to the device; the counts are scanned on the
 // device.  Records past the log's capacity fall back to the error bitmap.
-int resolve_impl(mxp_engine* eng, const mxp_bag_batch* batch, uint32_t variety, bool ids16, uint8_t* status,
+int resolve_impl(mxp_engine* eng, const mxp_bag_batch* batch, uint32_t variety, ResIds ids, uint8_t* status,
                  uint32_t* err_rule, uint64_t* sel_off, void* sel_rules, uint64_t sel_cap, uint64_t* ref_off,
                  mxp_attr_ref* refs, uint64_t ref_cap, const mxp_resolve_place* place = nullptr,
                  mxp_dbatch* pre = nullptr, uint64_t first_cap = 0) {
@@ -555,7 +648,7 @@ int resolve_impl(mxp_engine* eng, const mxp_bag_batch* batch, uint32_t variety, 
     J.eng = eng;
     J.batch = batch;
     J.variety = variety;
-    J.ids16 = ids16;
+    J.ids = ids;
     J.ref_off = ref_off;
     J.refs = refs;
     J.ref_cap = ref_cap;
@@ -569,11 +662,12 @@ int mxp_resolve_placed(mxp_engine* eng, mxp_dbatch* db, const mxp_bag_batch* bat
                        uint8_t* status, uint32_t* err_rule, uint64_t* sel_off, void* sel_rules,
                        const mxp_resolve_place& place, uint64_t first_cap) {
     if (!batch && db && db->wide) batch = &db->wide->view;  // (a narrow upload: its host view)
-    if (flags & ~(uint32_t)MXP_RESOLVE_IDS_U16) {
+    ResIds ids;
+    if (!resolve_ids_format(flags, &ids)) {
         if (eng && db) eng->recycle(db);
         return MXP_ERR_ARG;
     }
-    return resolve_impl(eng, batch, variety, (flags & MXP_RESOLVE_IDS_U16) != 0, status, err_rule, sel_off, sel_rules,
+    return resolve_impl(eng, batch, variety, ids, status, err_rule, sel_off, sel_rules,
                         0, nullptr, nullptr, 0, &place, db, first_cap);
 }
 
@@ -591,13 +685,15 @@ extern "C" {
 
 int mxp_resolve_batch(mxp_engine* eng, const mxp_bag_batch* batch, uint32_t variety, uint8_t* status,
                       uint32_t* err_rule, uint64_t* sel_off, uint32_t* sel_rules, uint64_t sel_cap) {
-    return resolve_impl(eng, batch, variety, false, status, err_rule, sel_off, sel_rules, sel_cap, nullptr, nullptr, 0);
+    return resolve_impl(eng, batch, variety, ResIds::U32, status, err_rule, sel_off, sel_rules, sel_cap, nullptr,
+                        nullptr, 0);
 }
 
 int mxp_resolve_batch_ex(mxp_engine* eng, const mxp_bag_batch* batch, uint32_t variety, uint32_t flags,
                          uint8_t* status, uint32_t* err_rule, uint64_t* sel_off, void* sel_rules, uint64_t sel_cap) {
-    if (flags & ~(uint32_t)MXP_RESOLVE_IDS_U16) return MXP_ERR_ARG;
-    return resolve_impl(eng, batch, variety, (flags & MXP_RESOLVE_IDS_U16) != 0, status, err_rule, sel_off, sel_rules,
+    ResIds ids;
+    if (!resolve_ids_format(flags, &ids)) return MXP_ERR_ARG;
+    return resolve_impl(eng, batch, variety, ids, status, err_rule, sel_off, sel_rules,
                         sel_cap, nullptr, nullptr, 0);
 }
 
@@ -605,11 +701,12 @@ int mxp_resolve_uploaded(mxp_engine* eng, mxp_dbatch* db, const mxp_bag_batch* b
                          uint8_t* status, uint32_t* err_rule, uint64_t* sel_off, void* sel_rules, uint64_t sel_cap) {
     if (!db) return MXP_ERR_ARG;
     if (!batch && db->wide) batch = &db->wide->view;  // (a narrow upload: its host view)
-    if (!eng || (flags & ~(uint32_t)MXP_RESOLVE_IDS_U16)) {
+    ResIds ids;
+    if (!eng || !resolve_ids_format(flags, &ids)) {
         if (eng) eng->recycle(db);
         return MXP_ERR_ARG;
     }
-    return resolve_impl(eng, batch, variety, (flags & MXP_RESOLVE_IDS_U16) != 0, status, err_rule, sel_off, sel_rules,
+    return resolve_impl(eng, batch, variety, ids, status, err_rule, sel_off, sel_rules,
                         sel_cap, nullptr, nullptr, 0, nullptr, db);
 }
 
@@ -617,13 +714,14 @@ int mxp_resolve_submit(mxp_engine* eng, mxp_dbatch* db, const mxp_bag_batch* bat
                        mxp_resolve_job** out) {
     std::unique_ptr<mxp_resolve_job> J(new mxp_resolve_job());
     J->db.reset(db);  // (taken over, whatever happens)
-    if (!eng || !db || !out || (flags & ~(uint32_t)MXP_RESOLVE_IDS_U16) || variety >= 32) return MXP_ERR_ARG;
+    ResIds ids;
+    if (!eng || !db || !out || !resolve_ids_format(flags, &ids) || variety >= 32) return MXP_ERR_ARG;
     if (!batch && db->wide) batch = &db->wide->view;  // (a narrow upload: its host view)
     if (!batch) return MXP_ERR_ARG;
     J->eng = eng;
     J->batch = batch;
     J->variety = variety;
-    J->ids16 = (flags & MXP_RESOLVE_IDS_U16) != 0;
+    J->ids = ids;
     if (int rc = resolve_begin(*J)) return rc;
     *out = J.release();
     return MXP_OK;
@@ -640,8 +738,8 @@ int mxp_resolve_refs(mxp_engine* eng, const mxp_bag_batch* batch, uint32_t varie
                      uint32_t* err_rule, uint64_t* sel_off, uint32_t* sel_rules, uint64_t sel_cap, uint64_t* ref_off,
                      mxp_attr_ref* refs, uint64_t ref_cap) {
     if (!ref_off) return MXP_ERR_ARG;
-    return resolve_impl(eng, batch, variety, false, status, err_rule, sel_off, sel_rules, sel_cap, ref_off, refs,
-                        ref_cap);
+    return resolve_impl(eng, batch, variety, ResIds::U32, status, err_rule, sel_off, sel_rules, sel_cap, ref_off,
+                        refs, ref_cap);
 }
 
 }  // extern "C"

@@ -294,6 +294,94 @@ class MxpError(RuntimeError):
     pass
 
 
+# ---------------------------------------------------------------- action list formats (include/mxp.h)
+RESOLVE_IDS_U16, RESOLVE_IDS_DELTA8 = 1, 2
+
+
+def _ids_format(ids16: bool, delta8: bool):
+    """(mxp_resolve_batch_ex flags, dtype of sel_rules); both formats at once: the library refuses."""
+    flags = (RESOLVE_IDS_U16 if ids16 else 0) | (RESOLVE_IDS_DELTA8 if delta8 else 0)
+    return flags, np.uint8 if delta8 else np.uint16 if ids16 else np.uint32
+
+
+def encode_delta8(off, ids):
+    """The reference encoder of MXP_RESOLVE_IDS_DELTA8: (id offsets [n + 1], rule ids) -> (byte
+    offsets u64[n + 1], stream u8).  Each request alone, prev = -1; per id d = id - prev - 1: one byte
+    d when 0 <= d <= 254, else FF and the id as two bytes, little-endian.  Canonical: the escape only
+    where one byte cannot express the step."""
+    off = np.asarray(off, dtype=np.int64)
+    ids = np.asarray(ids).astype(np.int64)
+    if off.ndim != 1 or len(off) < 1 or off[0] != 0 or off[-1] != len(ids) or np.any(np.diff(off) < 0):
+        raise ValueError("encode_delta8: offsets do not delimit the ids")
+    if len(ids) and (ids.min() < 0 or ids.max() > 65535):
+        raise ValueError("encode_delta8: rule id outside 0..65535")
+    prev = np.empty(len(ids), dtype=np.int64)
+    prev[1:] = ids[:-1]
+    starts = off[:-1][np.diff(off) > 0]
+    prev[starts] = -1
+    d = ids - prev - 1
+    esc = (d < 0) | (d > 254)
+    size = 1 + 2 * esc.astype(np.int64)
+    cum = np.concatenate([[0], np.cumsum(size)])
+    pos = cum[:-1]
+    stream = np.empty(int(cum[-1]), dtype=np.uint8)
+    stream[pos[~esc]] = d[~esc]
+    pe = pos[esc]
+    stream[pe] = 0xFF
+    stream[pe + 1] = ids[esc] & 0xFF
+    stream[pe + 2] = ids[esc] >> 8
+    return cum[off].astype(np.uint64), stream
+
+
+def decode_delta8(boff, stream):
+    """(byte offsets [n + 1], stream) of MXP_RESOLVE_IDS_DELTA8 -> (id offsets u64[n + 1], rule ids
+    u16).  boff may be a slice of a batch's offsets (boff[0] > 0).  ValueError when a request's range
+    ends inside an escape, or an id leaves 0..65535."""
+    boff = np.asarray(boff, dtype=np.int64)
+    if boff.ndim != 1 or len(boff) < 1 or np.any(np.diff(boff) < 0) or boff[0] < 0 or boff[-1] > len(stream):
+        raise ValueError("decode_delta8: offsets do not delimit the stream")
+    s = np.asarray(stream, dtype=np.uint8)[int(boff[0]):int(boff[-1])]
+    b = boff - boff[0]
+    L = len(s)
+    ff = s == 0xFF
+    # state[i] before byte i: 0 a code starts, 1 / 2 the escape's first / second id byte; -1 unknown.
+    # Known at every request's start and after two bytes that are not FF, whatever came before; the
+    # rest follows byte by byte from there (only the frontier is touched in each pass).
+    state = np.full(L + 1, -1, dtype=np.int8)
+    if L >= 2:
+        state[2:][~ff[:-1] & ~ff[1:]] = 0
+    state[b] = 0
+
+    def step(st, f):
+        return np.where(st == 0, np.where(f, 1, 0), np.where(st == 1, 2, 0)).astype(np.int8)
+    front = np.nonzero((state[:-1] >= 0) & (state[1:] < 0))[0]
+    while len(front):
+        state[front + 1] = step(state[front], ff[front])
+        front = front + 1
+        front = front[front < L]
+        front = front[state[front + 1] < 0]
+    # (a request's start, and the stream's end, inside an escape: the byte before leaves a state other than 0)
+    ends = b[b > 0]
+    if len(ends) and np.any(step(state[ends - 1], ff[ends - 1]) != 0):
+        raise ValueError("decode_delta8: stream truncated inside an escape")
+    ts = np.nonzero(state[:L] == 0)[0]  # where the codes start
+    off = np.searchsorted(ts, b, side="left").astype(np.int64)
+    m = len(ts)
+    esc = ff[ts]
+    first = np.zeros(m, dtype=bool)
+    first[off[:-1][np.diff(off) > 0]] = True
+    tse = ts[esc]
+    val = s[ts].astype(np.int64)  # d, or for an escape the id itself
+    val[esc] = s[tse + 1].astype(np.int64) | (s[tse + 2].astype(np.int64) << 8)
+    absolute = esc | first        # (a request's first id with prev = -1 is d itself)
+    c = np.cumsum(np.where(absolute, 0, val + 1))
+    r = np.maximum.accumulate(np.where(absolute, np.arange(m), 0))
+    ids = val[r] + c - c[r]
+    if m and ids.max() > 65535:
+        raise ValueError("decode_delta8: rule id above 65535")
+    return off.astype(np.uint64), ids.astype(np.uint16)
+
+
 class Engine:
     """One GPU (or a host-only compiler when device=-1) + one rule set."""
 
@@ -562,31 +650,34 @@ class Engine:
         self._check(self.lib.mxp_resolver_set(self.h, identity_attr.encode(), default_ns.encode(), ns,
                                               vm.ctypes.data, tcp.ctypes.data, em.ctypes.data, n), "mxp_resolver_set")
 
-    def resolve_arrays(self, batch: BagBatch, variety: int, cap: int = 0, ids16: bool = False, pinned: bool = False):
+    def resolve_arrays(self, batch: BagBatch, variety: int, cap: int = 0, ids16: bool = False, pinned: bool = False,
+                       delta8: bool = False):
         """mxp_resolve_batch -> (status u8[n], err_rule u32[n], sel_off u64[n + 1], sel_rules u32[...]):
         request q's selected rules are sel_rules[sel_off[q]:sel_off[q + 1]], in resolution order.
-        ids16: mxp_resolve_batch_ex with MXP_RESOLVE_IDS_U16 (sel_rules u16).  pinned: the outputs in
-        a pinned arena the engine object keeps (DMA straight into them; the arrays are views, valid
-        until the next pinned call)."""
+        ids16: mxp_resolve_batch_ex with MXP_RESOLVE_IDS_U16 (sel_rules u16).  delta8: with
+        MXP_RESOLVE_IDS_DELTA8 (sel_rules the u8 stream, sel_off and cap in bytes; decode_delta8).
+        pinned: the outputs in a pinned arena the engine object keeps (DMA straight into them; the
+        arrays are views, valid until the next pinned call)."""
         n = batch.n
         cap = cap or max(16, n * 4)
-        isz = 2 if ids16 else 4
+        flags, dt = _ids_format(ids16, delta8)
+        isz = dt().itemsize
 
         def outputs(cap):
             if not pinned:
                 return (np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint32), np.empty(n + 1, dtype=np.uint64),
-                        np.empty(cap, dtype=np.uint16 if ids16 else np.uint32))
+                        np.empty(cap, dtype=dt))
             need = n * 13 + 8 + cap * isz + 4 * 64
             if getattr(self, "_out_arena", None) is None or self._out_arena.size < need:
                 self._out_arena = PinnedArena(int(need * 1.25))
             a = self._out_arena
             a.used = 0
             return (a.empty(n, np.uint8), a.empty(n, np.uint32), a.empty(n + 1, np.uint64),
-                    a.empty(cap, np.uint16 if ids16 else np.uint32))
+                    a.empty(cap, dt))
         for _ in range(2):
             status, err_rule, off, sel = outputs(cap)
-            if ids16:
-                rc = self.lib.mxp_resolve_batch_ex(self.h, ctypes.byref(batch.c_struct()), variety, 1,
+            if flags:
+                rc = self.lib.mxp_resolve_batch_ex(self.h, ctypes.byref(batch.c_struct()), variety, flags,
                                                    status.ctypes.data, err_rule.ctypes.data, off.ctypes.data,
                                                    sel.ctypes.data, cap)
             else:
@@ -599,42 +690,47 @@ class Engine:
             break
         return status, err_rule, off, sel[:int(off[n])]
 
-    def resolve_uploaded(self, db: "DeviceBatch", variety: int, cap: int, ids16: bool = False):
+    def resolve_uploaded(self, db: "DeviceBatch", variety: int, cap: int, ids16: bool = False, delta8: bool = False):
         """mxp_resolve_uploaded: Resolve a batch uploaded before (db is taken over) -> as resolve_arrays."""
         batch, cs = db._src
         n = batch.n
+        flags, dt = _ids_format(ids16, delta8)
         status, err_rule = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint32)
-        off, sel = np.empty(n + 1, dtype=np.uint64), np.empty(max(cap, 1), dtype=np.uint16 if ids16 else np.uint32)
+        off, sel = np.empty(n + 1, dtype=np.uint64), np.empty(max(cap, 1), dtype=dt)
         h, db.h = db.h, None
         self._check(self.lib.mxp_resolve_uploaded(self.h, h, ctypes.byref(cs) if cs is not None else None, variety,
-                                                  1 if ids16 else 0,
+                                                  flags,
                                                   status.ctypes.data, err_rule.ctypes.data, off.ctypes.data,
                                                   sel.ctypes.data, cap), "mxp_resolve_uploaded")
         return status, err_rule, off, sel[:int(off[n])]
 
-    def resolve_submit(self, db: "DeviceBatch", variety: int, ids16: bool = False):
+    def resolve_submit(self, db: "DeviceBatch", variety: int, ids16: bool = False, delta8: bool = False):
         """mxp_resolve_submit: the evaluation of an uploaded batch enqueued (db taken over) -> a job for
         resolve_finish; the engine takes only an upload in between."""
         batch, cs = db._src
+        flags, dt = _ids_format(ids16, delta8)
         h, db.h = db.h, None
         job = _VP()
         self._check(self.lib.mxp_resolve_submit(self.h, h, ctypes.byref(cs) if cs is not None else None, variety,
-                                                1 if ids16 else 0, ctypes.byref(job)), "mxp_resolve_submit")
-        return (job, batch.n, ids16)
+                                                flags, ctypes.byref(job)), "mxp_resolve_submit")
+        # (db._src kept: the C job points into the host batch until finish)
+        return (job, batch.n, dt, db._src)
 
     def resolve_finish(self, job, cap: int):
         """mxp_resolve_finish -> (status, err_rule, sel_off, sel_rules) as resolve_uploaded."""
-        h, n, ids16 = job
+        h, n, dt, _src = job
         status, err_rule = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint32)
-        off, sel = np.empty(n + 1, dtype=np.uint64), np.empty(max(cap, 1), dtype=np.uint16 if ids16 else np.uint32)
+        off, sel = np.empty(n + 1, dtype=np.uint64), np.empty(max(cap, 1), dtype=dt)
         self._check(self.lib.mxp_resolve_finish(h, status.ctypes.data, err_rule.ctypes.data, off.ctypes.data,
                                                 sel.ctypes.data, cap), "mxp_resolve_finish")
         return status, err_rule, off, sel[:int(off[n])]
 
-    def resolve(self, batch: BagBatch, variety: int, ids16: bool = False):
+    def resolve(self, batch: BagBatch, variety: int, ids16: bool = False, delta8: bool = False):
         """Resolve every request (mxp_resolve_batch) -> (status u8[n], err_rule u32[n], selected:
-        list of per-request rule-id arrays in resolution order)."""
-        status, err_rule, off, sel = self.resolve_arrays(batch, variety, ids16=ids16)
+        list of per-request rule-id arrays in resolution order; delta8: decoded from the stream)."""
+        status, err_rule, off, sel = self.resolve_arrays(batch, variety, ids16=ids16, delta8=delta8)
+        if delta8:
+            off, sel = decode_delta8(off, sel)
         return status, err_rule, [sel[int(off[q]):int(off[q + 1])] for q in range(batch.n)]
 
     # ------------------------------------------------------------------ list adapter
@@ -1175,12 +1271,14 @@ class Group:
 
     # ------------------------------------------------------------------ Resolve
     def resolve_arrays(self, shards: Sequence[BagBatch], variety: int, cap: int = 0, ids16: bool = False, out=None,
-                       uploaded: "GroupBatch" = None):
+                       uploaded: "GroupBatch" = None, delta8: bool = False):
         """mxp_group_resolve_batch over shards (member k's requests = shards[k]) -> (status, err_rule,
         sel_off, sel_rules) of the concatenated batch.  out: preallocated (status, err_rule, sel_off,
         sel) arrays (e.g. pinned), reused when large enough.  uploaded: the shards' GroupBatch from an
-        earlier upload (mxp_group_resolve_uploaded; taken over -- no retry when cap is short)."""
+        earlier upload (mxp_group_resolve_uploaded; taken over -- no retry when cap is short).
+        delta8: MXP_RESOLVE_IDS_DELTA8 (sel the u8 stream, sel_off and cap in bytes)."""
         n = sum(b.n for b in shards) if shards is not None else uploaded.n
+        flags, dt = _ids_format(ids16, delta8)
         if uploaded is None:
             cs, arr = self._shards(shards)
         elif uploaded._src[1] is None:  # (narrow uploads: the members keep the host views)
@@ -1195,15 +1293,15 @@ class Group:
             else:
                 status, err_rule, off = (np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint32),
                                          np.empty(n + 1, dtype=np.uint64))
-                sel = np.empty(cap, dtype=np.uint16 if ids16 else np.uint32)
+                sel = np.empty(cap, dtype=dt)
             if uploaded is not None:
                 h, uploaded.h = uploaded.h, None
-                rc = self.lib.mxp_group_resolve_uploaded(self.h, h, arr, len(cs), variety, 1 if ids16 else 0,
+                rc = self.lib.mxp_group_resolve_uploaded(self.h, h, arr, len(cs), variety, flags,
                                                          status.ctypes.data, err_rule.ctypes.data, off.ctypes.data,
                                                          sel.ctypes.data, len(sel))
                 self._check(rc, "mxp_group_resolve_uploaded")
                 break
-            rc = self.lib.mxp_group_resolve_batch(self.h, arr, len(cs), variety, 1 if ids16 else 0, status.ctypes.data,
+            rc = self.lib.mxp_group_resolve_batch(self.h, arr, len(cs), variety, flags, status.ctypes.data,
                                                   err_rule.ctypes.data, off.ctypes.data, sel.ctypes.data, len(sel))
             if rc == 4:
                 cap = int(off[n])
@@ -1213,7 +1311,7 @@ class Group:
             break
         return status[:n], err_rule[:n], off[:n + 1], sel[:int(off[n])]
 
-    def resolve_submit(self, uploaded: "GroupBatch", variety: int, ids16: bool = False):
+    def resolve_submit(self, uploaded: "GroupBatch", variety: int, ids16: bool = False, delta8: bool = False):
         """mxp_group_resolve_submit: every member's evaluation of the uploaded shards enqueued (taken
         over) -> a job for resolve_finish; only an upload may come in between."""
         if uploaded._src[1] is None:  # (narrow uploads: the members keep the host views)
@@ -1221,28 +1319,31 @@ class Group:
         else:
             cs = uploaded._src[1]
             arr = (_VP * len(cs))(*[ctypes.addressof(c) for c in cs])
+        flags, dt = _ids_format(ids16, delta8)
         h, uploaded.h = uploaded.h, None
         job = _VP()
-        self._check(self.lib.mxp_group_resolve_submit(self.h, h, arr, self.n, variety, 1 if ids16 else 0,
+        self._check(self.lib.mxp_group_resolve_submit(self.h, h, arr, self.n, variety, flags,
                                                       ctypes.byref(job)), "mxp_group_resolve_submit")
-        return (job, uploaded.n, ids16, uploaded._src)
+        return (job, uploaded.n, dt, uploaded._src)
 
     def resolve_finish(self, job, cap: int, out=None):
         """mxp_group_resolve_finish -> (status, err_rule, sel_off, sel_rules) of the whole batch."""
-        h, n, ids16, _src = job
+        h, n, dt, _src = job
         if out is not None and len(out[3]) >= cap:
             status, err_rule, off, sel = out
         else:
             status, err_rule, off = (np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint32),
                                      np.empty(n + 1, dtype=np.uint64))
-            sel = np.empty(max(cap, 1), dtype=np.uint16 if ids16 else np.uint32)
+            sel = np.empty(max(cap, 1), dtype=dt)
         self._check(self.lib.mxp_group_resolve_finish(self.h, h, status.ctypes.data, err_rule.ctypes.data,
                                                       off.ctypes.data, sel.ctypes.data, len(sel)),
                     "mxp_group_resolve_finish")
         return status[:n], err_rule[:n], off[:n + 1], sel[:int(off[n])]
 
-    def resolve(self, shards: Sequence[BagBatch], variety: int, ids16: bool = False):
-        status, err_rule, off, sel = self.resolve_arrays(shards, variety, ids16=ids16)
+    def resolve(self, shards: Sequence[BagBatch], variety: int, ids16: bool = False, delta8: bool = False):
+        status, err_rule, off, sel = self.resolve_arrays(shards, variety, ids16=ids16, delta8=delta8)
+        if delta8:
+            off, sel = decode_delta8(off, sel)
         return status, err_rule, [sel[int(off[q]):int(off[q + 1])] for q in range(len(status))]
 
     def pair_error(self, request: int, rule: int) -> str:
