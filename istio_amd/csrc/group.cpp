@@ -347,6 +347,84 @@ int mxp_resolve_finish_placed(mxp_resolve_job* job, uint8_t* status, uint32_t* e
                               void* sel_rules, const mxp_resolve_place& place, uint64_t first_cap = 0);
 void mxp_resolve_job_free(mxp_resolve_job* job);
 
+namespace {
+
+// where the members of a group Resolve meet, once, when each knows its own count
+struct Rendezvous {
+    std::mutex mu;
+    std::condition_variable cv;
+    uint32_t arrived = 0;
+    std::vector<uint64_t> total;
+    std::vector<bool> in;
+    explicit Rendezvous(uint32_t n) : total(n, 0), in(n, false) {}
+    void arrive(uint32_t k, uint64_t t) {  // (k's count; idempotent per member)
+        std::lock_guard<std::mutex> l(mu);
+        if (in[k]) return;
+        in[k] = true;
+        total[k] = t;
+        if (++arrived == total.size()) cv.notify_all();
+    }
+    void wait() {
+        std::unique_lock<std::mutex> l(mu);
+        cv.wait(l, [&] { return arrived == total.size(); });
+    }
+};
+
+// member k's Resolve into (status, err_rule, sel_off) at its first request, its ids placed by `place`;
+// first_cap: the whole list's capacity for member 0, else 0 (mxp_resolve_placed / _finish_placed)
+using MemberResolve = std::function<int(uint32_t k, uint8_t* status, uint32_t* err_rule, uint64_t* sel_off,
+                                        const mxp_resolve_place& place, uint64_t first_cap)>;
+
+// The finish of every group Resolve.  Every member resolves its shard (lo[k], cnt[k] requests)
+// straight into the caller's arrays: status / err_rule at its first request, its batch-local offsets
+// at sel_off + lo[k], and its rule ids at the place the members' counts give it -- the members meet
+// when each knows its own count, before downloading the ids.  Then the offsets are rebased.
+int group_resolve_finish(mxp_group* g, const std::vector<uint64_t>& lo, const std::vector<uint64_t>& cnt, uint8_t* status,
+                         uint32_t* err_rule, uint64_t* sel_off, uint64_t sel_cap, const MemberResolve& member) {
+    const uint32_t n_shards = g->size();
+    Rendezvous rv(n_shards);
+    std::atomic<bool> failed{false};
+    int rc = g->each([&](uint32_t k) -> int {
+        const mxp_resolve_place place = [&](uint64_t t) -> int64_t {
+            rv.arrive(k, t);
+            rv.wait();
+            if (failed.load()) return -1;
+            uint64_t base = 0, sum = 0;
+            for (uint32_t j = 0; j < n_shards; j++) {
+                if (j < k) base += rv.total[j];
+                sum += rv.total[j];
+            }
+            return sum <= sel_cap ? (int64_t)base : -1;
+        };
+        const int r = member(k, status + lo[k], err_rule + lo[k], sel_off + lo[k], place, k == 0 ? sel_cap : 0);
+        if (r && r != MXP_ERR_NOMEM) failed.store(true);
+        rv.arrive(k, 0);  // (a member that failed before its count still lets the others go on)
+        return r == MXP_ERR_NOMEM ? MXP_OK : r;
+    });
+    if (rc) return rc;
+    uint64_t total = 0;
+    std::vector<uint64_t> base(n_shards, 0);
+    for (uint32_t k = 0; k < n_shards; k++) {
+        base[k] = total;
+        total += rv.total[k];
+    }
+    // the batch-local offsets rebased (member 0's are already global); each member's first entry is
+    // its base (the engines leave it alone: it is the previous member's last entry)
+    rc = g->each([&](uint32_t k) -> int {
+        const uint64_t n = cnt[k], b = base[k];
+        if (!n) return MXP_OK;
+        sel_off[lo[k]] = b;
+        if (b)
+            for (uint64_t i = 1; i < n; i++) sel_off[lo[k] + i] += b;
+        return MXP_OK;
+    });
+    sel_off[lo[n_shards]] = total;
+    if (rc) return rc;
+    return total <= sel_cap ? MXP_OK : MXP_ERR_NOMEM;
+}
+
+}  // namespace
+
 extern "C" {
 
 void mxp_group_shard_bounds(uint64_t n_total, uint32_t member, uint32_t n_members, uint64_t* lo, uint64_t* hi) {
@@ -965,74 +1043,13 @@ static int group_resolve(mxp_group* g, mxp_gbatch* gb, const mxp_bag_batch* cons
     std::vector<uint64_t> cnt(n_shards);
     for (uint32_t k = 0; k < n_shards; k++) cnt[k] = shards[k]->n_requests;
     g->set_bounds(cnt);
-    // Every member resolves its shard straight into the caller's arrays: status / err_rule at its
-    // first request, its batch-local offsets at sel_off + lo (the boundary entry each member shares with
-    // the next is rewritten below), and its rule ids at the place the members' counts give it -- the
-    // members meet once (Rendezvous), when each knows its own count, before downloading the ids.
-    struct Rendezvous {
-        std::mutex mu;
-        std::condition_variable cv;
-        uint32_t arrived = 0, n = 0;
-        std::vector<uint64_t> total;
-        std::vector<bool> in;
-        uint64_t sum = 0;
-        void arrive(uint32_t k, uint64_t t) {  // (k's count; idempotent per member)
-            std::lock_guard<std::mutex> l(mu);
-            if (in[k]) return;
-            in[k] = true;
-            total[k] = t;
-            if (++arrived == n) cv.notify_all();
-        }
-        void wait() {
-            std::unique_lock<std::mutex> l(mu);
-            cv.wait(l, [&] { return arrived == n; });
-        }
-    } rv;
-    rv.n = n_shards;
-    rv.total.assign(n_shards, 0);
-    rv.in.assign(n_shards, false);
-    std::atomic<bool> failed{false};
-    int rc = g->each([&](uint32_t k) -> int {
-        const uint64_t lo = g->lo[k];
-        const mxp_resolve_place place = [&](uint64_t t) -> int64_t {
-            rv.arrive(k, t);
-            rv.wait();
-            if (failed.load()) return -1;
-            uint64_t base = 0, sum = 0;
-            for (uint32_t j = 0; j < n_shards; j++) {
-                if (j < k) base += rv.total[j];
-                sum += rv.total[j];
-            }
-            return sum <= sel_cap ? (int64_t)base : -1;
-        };
+    const MemberResolve member = [&](uint32_t k, uint8_t* st, uint32_t* er, uint64_t* off, const mxp_resolve_place& place,
+                                     uint64_t first_cap) {
         mxp_dbatch* db = nullptr;
         if (gb) std::swap(db, gb->db[k]);  // (taken over by the member's Resolve)
-        const int r = mxp_resolve_placed(g->m[k].eng, db, shards[k], variety, flags, status + lo, err_rule + lo,
-                                         sel_off + lo, sel_rules, place, k == 0 ? sel_cap : 0);
-        if (r && r != MXP_ERR_NOMEM) failed.store(true);
-        rv.arrive(k, 0);  // (a member that failed before its count still lets the others go on)
-        return r == MXP_ERR_NOMEM ? MXP_OK : r;
-    });
-    if (rc) return rc;
-    uint64_t total = 0;
-    std::vector<uint64_t> base(n_shards, 0);
-    for (uint32_t k = 0; k < n_shards; k++) {
-        base[k] = total;
-        total += rv.total[k];
-    }
-    // the batch-local offsets rebased (member 0's are already global); each member's first entry is
-    // its base (the engines leave it alone: it is the previous member's last entry)
-    rc = g->each([&](uint32_t k) -> int {
-        const uint64_t lo = g->lo[k], n = cnt[k], b = base[k];
-        if (!n) return MXP_OK;
-        sel_off[lo] = b;
-        if (b)
-            for (uint64_t i = 1; i < n; i++) sel_off[lo + i] += b;
-        return MXP_OK;
-    });
-    sel_off[g->lo[n_shards]] = total;
-    if (rc) return rc;
-    return total <= sel_cap ? MXP_OK : MXP_ERR_NOMEM;
+        return mxp_resolve_placed(g->m[k].eng, db, shards[k], variety, flags, st, er, off, sel_rules, place, first_cap);
+    };
+    return group_resolve_finish(g, g->lo, cnt, status, err_rule, sel_off, sel_cap, member);
 }
 
 // ---- the two-call Resolve (mxp_group_resolve_submit / _finish; the member calls: above extern "C")
@@ -1074,79 +1091,20 @@ int mxp_group_resolve_submit(mxp_group* g, mxp_gbatch* gb, const mxp_bag_batch* 
 int mxp_group_resolve_finish(mxp_group* g, mxp_gresolve* r0, uint8_t* status, uint32_t* err_rule, uint64_t* sel_off,
                              void* sel_rules, uint64_t sel_cap) {
     std::unique_ptr<mxp_gresolve> r(r0);
-    if (!g || !r || r->jobs.size() != g->size()) {
-        if (r)
-            for (mxp_resolve_job*& j : r->jobs) mxp_resolve_job_free(j), j = nullptr;
-        return MXP_ERR_ARG;
-    }
-    auto drop = [&] {
-        for (mxp_resolve_job*& j : r->jobs)
-            if (j) mxp_resolve_job_free(j), j = nullptr;
-    };
-    if (!status || !err_rule || !sel_off || (sel_cap && !sel_rules)) {
-        drop();
+    if (!r) return MXP_ERR_ARG;
+    if (!g || r->jobs.size() != g->size() || !status || !err_rule || !sel_off || (sel_cap && !sel_rules)) {
+        for (mxp_resolve_job* j : r->jobs) mxp_resolve_job_free(j);  // (submitted, never finished)
         return MXP_ERR_ARG;
     }
     DeviceGuard guard;
-    const uint32_t n_shards = g->size();
     g->lo = r->lo;  // (pair errors and locate refer to this batch again)
-    // as group_resolve: every member resolves into the caller's arrays, its ids at the base the
-    // members agree on once each knows its own count
-    std::mutex mu;
-    std::condition_variable cv;
-    uint32_t arrived = 0;
-    std::vector<uint64_t> total_k(n_shards, 0);
-    std::vector<bool> in(n_shards, false);
-    auto arrive = [&](uint32_t k, uint64_t t) {
-        std::lock_guard<std::mutex> l(mu);
-        if (in[k]) return;
-        in[k] = true;
-        total_k[k] = t;
-        if (++arrived == n_shards) cv.notify_all();
-    };
-    std::atomic<bool> failed{false};
-    int rc = g->each([&](uint32_t k) -> int {
-        const uint64_t lo = r->lo[k];
-        const mxp_resolve_place place = [&](uint64_t t) -> int64_t {
-            arrive(k, t);
-            {
-                std::unique_lock<std::mutex> l(mu);
-                cv.wait(l, [&] { return arrived == n_shards; });
-            }
-            if (failed.load()) return -1;
-            uint64_t base = 0, sum = 0;
-            for (uint32_t j = 0; j < n_shards; j++) {
-                if (j < k) base += total_k[j];
-                sum += total_k[j];
-            }
-            return sum <= sel_cap ? (int64_t)base : -1;
-        };
+    const MemberResolve member = [&](uint32_t k, uint8_t* st, uint32_t* er, uint64_t* off, const mxp_resolve_place& place,
+                                     uint64_t first_cap) {
         mxp_resolve_job* job = nullptr;
-        std::swap(job, r->jobs[k]);
-        const int rr = mxp_resolve_finish_placed(job, status + lo, err_rule + lo, sel_off + lo, sel_rules, place,
-                                                 k == 0 ? sel_cap : 0);
-        if (rr && rr != MXP_ERR_NOMEM) failed.store(true);
-        arrive(k, 0);  // (a member that failed before its count still lets the others go on)
-        return rr == MXP_ERR_NOMEM ? MXP_OK : rr;
-    });
-    if (rc) return rc;
-    uint64_t total = 0;
-    std::vector<uint64_t> base(n_shards, 0);
-    for (uint32_t k = 0; k < n_shards; k++) {
-        base[k] = total;
-        total += total_k[k];
-    }
-    rc = g->each([&](uint32_t k) -> int {  // (the batch-local offsets rebased, as group_resolve)
-        const uint64_t lo = r->lo[k], n = r->cnt[k], b = base[k];
-        if (!n) return MXP_OK;
-        sel_off[lo] = b;
-        if (b)
-            for (uint64_t i = 1; i < n; i++) sel_off[lo + i] += b;
-        return MXP_OK;
-    });
-    sel_off[r->lo[n_shards]] = total;
-    if (rc) return rc;
-    return total <= sel_cap ? MXP_OK : MXP_ERR_NOMEM;
+        std::swap(job, r->jobs[k]);  // (taken over by the member's finish)
+        return mxp_resolve_finish_placed(job, st, er, off, sel_rules, place, first_cap);
+    };
+    return group_resolve_finish(g, r->lo, r->cnt, status, err_rule, sel_off, sel_cap, member);
 }
 
 int mxp_group_resolve_batch(mxp_group* g, const mxp_bag_batch* const* shards, uint32_t n_shards, uint32_t variety,

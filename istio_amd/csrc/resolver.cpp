@@ -5,6 +5,7 @@
 // (:180-199), filterActions (:202-238).  The host derives each request's namespace and TCP flag
 // from its bag exactly as destAndNamespace / filterActions do; the GPU walks the namespace rule
 // ranges over the bitmaps mxp_eval_kernel / mxp_index_kernel produced.
+#include <cstddef>
 #include <cstring>
 #include <numeric>
 #include <string_view>
@@ -228,10 +229,40 @@ struct mxp_resolve_job {
 
 namespace {
 
+// mxp_launch_resolve's passes (the table above it in resolve.hip)
+enum ResPass : int { kCount = 0, kWrite = 1, kScan = 2, kTileCount = 3, kTileWrite = 4, kPairsCount = 5, kPairsWrite = 6 };
+
+// eng->res_small by field: the pinned 64-byte block a Resolve's small counts are downloaded into
+struct ResSmall {
+    uint32_t err_cnt[4];    // a compact Resolve's d_errcount: [0] records, [2] class records
+    uint32_t pairs_ovf[2];  // ... and the pairs past their lists / slots
+    uint32_t unused[2];
+    uint64_t ids_total;     // a delta8 Resolve's id count (its sel_off counts bytes)
+};
+static_assert(offsetof(ResSmall, ids_total) == 32 && sizeof(ResSmall) <= 64, "res_small as engine_impl.h describes it");
+
+int res_small(mxp_engine* eng, ResSmall** out) {
+    hipError_t e;
+    if (!eng->res_small && (e = hipHostMalloc((void**)&eng->res_small, 64, hipHostMallocDefault)) != hipSuccess) {
+        eng->res_small = nullptr;
+        return eng->hipfail(e, "pinned counters");
+    }
+    *out = reinterpret_cast<ResSmall*>(eng->res_small);
+    return MXP_OK;
+}
+
+// src into d (grown to hold it) on the engine's stream
+int upload(mxp_engine* eng, DevBuf& d, const void* src, size_t bytes, const char* what) {
+    hipError_t e;
+    if ((e = d.reserve(bytes)) != hipSuccess) return eng->hipfail(e, what);
+    if (bytes && (e = hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, eng->stream)) != hipSuccess)
+        return eng->hipfail(e, what);
+    return MXP_OK;
+}
+
 int resolve_begin(mxp_resolve_job& J) {
     mxp_engine* eng = J.eng;
     const mxp_bag_batch* batch = J.batch;
-    const uint32_t variety = J.variety;
     mxp_dbatch* pre = J.db.get();
     if (pre && (J.ref_off || pre->n != batch->n_requests))
         return eng->fail(MXP_ERR_ARG, "resolve: the uploaded batch is not this batch");
@@ -253,42 +284,34 @@ int resolve_begin(mxp_resolve_job& J) {
     // caller until the kernels end (r6_s25: 0.79 ms)
     // (kept on the device while the configuration and variety stay: four pageable copies a call,
     // ~0.1 ms of the caller's time, before)
-    DevBuf &d_info = eng->res_info, &d_lo = eng->res_lo, &d_hi = eng->res_hi, &d_amask = eng->res_amask,
-           &d_empty = eng->res_empty;
-    auto up = [&](DevBuf& d, const void* src, size_t bytes, const char* what) -> int {
-        if ((e = d.reserve(bytes)) != hipSuccess) return eng->hipfail(e, what);
-        if (bytes && (e = hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, eng->stream)) != hipSuccess)
-            return eng->hipfail(e, what);
-        return MXP_OK;
-    };
-    const uint64_t tab_key = eng->res_gen << 6 | variety;
+    DevBuf& d_info = eng->res_info;
+    const uint64_t tab_key = eng->res_gen << 6 | J.variety;
     if (eng->res_tab_key != tab_key) {
         std::vector<uint32_t> amask(2 * (size_t)W, 0), empty(W, 0);  // per-word masks: variety / tcp, empty matches
         bool any_empty = false;
         for (uint32_t r = 0; r < NR; r++) {
             const uint32_t bit = 1u << (r & 31);
-            if ((R.vmask[r] >> variety) & 1u) amask[(size_t)R.tcp[r] * W + r / 32] |= bit;
+            if ((R.vmask[r] >> J.variety) & 1u) amask[(size_t)R.tcp[r] * W + r / 32] |= bit;
             if (R.empty[r]) {
                 empty[r / 32] |= bit;
                 any_empty = true;
             }
         }
         eng->res_tab_key = ~0ull;  // (until every table is up)
-        if ((rc = up(d_lo, R.ns_lo.data(), R.ns_lo.size() * 4, "upload ns_lo"))) return rc;
-        if ((rc = up(d_hi, R.ns_hi.data(), R.ns_hi.size() * 4, "upload ns_hi"))) return rc;
-        if ((rc = up(d_amask, amask.data(), amask.size() * 4, "upload amask"))) return rc;
-        if ((rc = up(d_empty, empty.data(), empty.size() * 4, "upload empty"))) return rc;
+        if ((rc = upload(eng, eng->res_lo, R.ns_lo.data(), R.ns_lo.size() * 4, "upload ns_lo"))) return rc;
+        if ((rc = upload(eng, eng->res_hi, R.ns_hi.data(), R.ns_hi.size() * 4, "upload ns_hi"))) return rc;
+        if ((rc = upload(eng, eng->res_amask, amask.data(), amask.size() * 4, "upload amask"))) return rc;
+        if ((rc = upload(eng, eng->res_empty, empty.data(), empty.size() * 4, "upload empty"))) return rc;
         eng->res_tab_key = tab_key;
         eng->res_any_empty = any_empty;
     }
-    const bool any_empty = eng->res_any_empty;
     J.compact = !J.ref_off && !(eng->debug_flags & kResolveBitmap);
     if (J.compact) {
         if (eng->device >= 0 && (e = eng->res_flags.reserve(n ? n : 1)) != hipSuccess) return eng->hipfail(e, "alloc flags");
         // pair Resolve: the selected rules from the evaluation's deferred pairs, the bitmap left
         // unwritten, where the plan allows it (the launch decides); rules with an empty match are
         // selected without a pair, so their sets keep the bitmap
-        eng->pair_req = eng->resolve_pairs != 0 && !any_empty;
+        eng->pair_req = eng->resolve_pairs != 0 && !eng->res_any_empty;
         if (pre) {
             rc = eng->evaluate_uploaded(J.db.get(), dm, de, nullptr, eng->res_flags.as<uint8_t>());
         } else {
@@ -328,138 +351,129 @@ int resolve_begin(mxp_resolve_job& J) {
         request_info(eng, batch, &J.info);
         J.hinfo = J.info.data();
         eng->trace_mark("request namespaces (host)");
-        if ((rc = up(d_info, J.info.data(), J.info.size() * 4, "upload nsinfo"))) return rc;
+        if ((rc = upload(eng, d_info, J.info.data(), J.info.size() * 4, "upload nsinfo"))) return rc;
     }
     return MXP_OK;
 }
 
-int resolve_end(mxp_resolve_job& J, uint8_t* status, uint32_t* err_rule, uint64_t* sel_off, void* sel_rules,
-                uint64_t sel_cap, const mxp_resolve_place* place) {
+// ---- resolve_end's stages, in the order its driver (below them) runs them
+
+// The resolve kernels' argument block over the engine's scratch, grown to this batch.
+int resolve_args(mxp_resolve_job& J, mxp_resolve_args* out) {
     mxp_engine* eng = J.eng;
-    const mxp_bag_batch* batch = J.batch;
-    const uint32_t variety = J.variety, n = J.n, W = J.W;
-    // (delta8: the u16 list into engine scratch, coded from there)
-    const bool d8 = J.ids == ResIds::DELTA8, ids16 = J.ids != ResIds::U32, compact = J.compact;
-    uint64_t* ref_off = J.ref_off;
-    mxp_attr_ref* refs = J.refs;
-    const uint64_t ref_cap = J.ref_cap;
-    auto& db = J.db;
-    auto& recs = J.recs;
-    auto& info = J.info;
-    const uint32_t* hinfo = J.hinfo;
-    const auto& R = eng->resolver;
-    DevBuf& dm = eng->res_dm;
-    DevBuf& de = eng->res_de;
-    DevBuf &d_info = eng->res_info, &d_lo = eng->res_lo, &d_hi = eng->res_hi, &d_amask = eng->res_amask,
-           &d_empty = eng->res_empty, &d_status = eng->res_status, &d_err_rule = eng->res_err_rule,
-           &d_count = eng->res_count, &d_off = eng->res_off, &d_sel = eng->res_sel;
+    const size_t n = J.n, grid = (J.n + 255u) / 256u;
+    hipError_t e;
+    if ((e = eng->res_status.reserve(n)) != hipSuccess) return eng->hipfail(e, "alloc status");
+    if ((e = eng->res_err_rule.reserve(n * 4)) != hipSuccess) return eng->hipfail(e, "alloc err_rule");
+    if ((e = eng->res_count.reserve(n * 4)) != hipSuccess) return eng->hipfail(e, "alloc count");
+    if ((e = eng->res_bsum.reserve(grid * 8 + 8)) != hipSuccess) return eng->hipfail(e, "alloc block sums");
+    if ((e = eng->res_off.reserve((n + 1) * 8)) != hipSuccess) return eng->hipfail(e, "alloc sel_off");
+    if ((e = eng->res_stash.reserve(n * 16 + 16)) != hipSuccess) return eng->hipfail(e, "alloc stash");
+    mxp_resolve_args& A = *out;
+    memset(&A, 0, sizeof A);
+    A.n = J.n;
+    A.n_words = J.W;
+    A.nsinfo = eng->res_info.as<uint32_t>();
+    A.ns_lo = eng->res_lo.as<uint32_t>();
+    A.ns_hi = eng->res_hi.as<uint32_t>();
+    A.default_id = eng->resolver.default_id;
+    A.amask = eng->res_amask.as<uint32_t>();
+    A.empty = eng->res_empty.as<uint32_t>();
+    A.match = eng->res_dm.as<uint32_t>();
+    A.err = J.compact ? nullptr : eng->res_de.as<uint32_t>();
+    A.status = eng->res_status.as<uint8_t>();
+    A.err_rule = eng->res_err_rule.as<uint32_t>();
+    A.count = eng->res_count.as<uint32_t>();
+    A.block_sum = eng->res_bsum.as<uint64_t>();
+    A.sel_off_out = eng->res_off.as<uint64_t>();
+    A.sel_off = eng->res_off.as<uint64_t>();
+    A.ids16 = J.ids != ResIds::U32 ? 1u : 0u;
+    A.stash = (uint4*)eng->res_stash.p;
+    return MXP_OK;
+}
+
+// Error triage of a compact evaluation: where the resolve kernels find each request's first error.
+// Waits for the evaluation (the log's counts come back), then one of three: records past the log's
+// capacity -- the error bitmap after all (A.err); records only -- first errors on the device
+// (A.err_in, A.err_rank); class records -- expanded and ranked on the host (A.err_in; *collected).
+// J.pairs.on is cleared wherever the evaluation ended up writing the bitmaps.
+int triage_errors(mxp_resolve_job& J, mxp_resolve_args& A, bool* collected) {
+    mxp_engine* eng = J.eng;
+    const uint32_t n = J.n;
+    DevBuf &dm = eng->res_dm, &de = eng->res_de;
     hipError_t e;
     int rc;
-    auto up = [&](DevBuf& d, const void* src, size_t bytes, const char* what) -> int {
-        if ((e = d.reserve(bytes)) != hipSuccess) return eng->hipfail(e, what);
-        if (bytes && (e = hipMemcpyAsync(d.p, src, bytes, hipMemcpyHostToDevice, eng->stream)) != hipSuccess)
-            return eng->hipfail(e, what);
+    ResSmall* hs;
+    if ((rc = res_small(eng, &hs))) return rc;
+    // (into pinned memory: both copies queued, one synchronisation)
+    hs->pairs_ovf[0] = hs->pairs_ovf[1] = 0;
+    if ((e = hipMemcpyAsync(hs->err_cnt, eng->d_errcount.p, 16, hipMemcpyDeviceToHost, eng->stream)) != hipSuccess ||
+        (J.pairs.on &&
+         (e = hipMemcpyAsync(hs->pairs_ovf, J.pairs.ovf_n, 8, hipMemcpyDeviceToHost, eng->stream)) != hipSuccess) ||
+        (e = hipStreamSynchronize(eng->stream)) != hipSuccess)
+        return eng->hipfail(e, "download errcount");
+    const uint32_t n_recs = hs->err_cnt[0], n_class = hs->err_cnt[2];
+    // (pairs past their lists or slots: the fills stored the bitmap after all -- read it)
+    J.pairs_ovf = hs->pairs_ovf[0];
+    J.recs_n = n_recs;
+    J.class_recs_n = n_class;
+    if (J.pairs_ovf) J.pairs.on = false;
+    if ((e = eng->res_err_in.reserve((size_t)n * 4 + 4)) != hipSuccess) return eng->hipfail(e, "alloc err_in");
+    if (n && (e = hipMemsetAsync(eng->res_err_in.p, 0xFF, (size_t)n * 4, eng->stream)) != hipSuccess)
+        return eng->hipfail(e, "reset err_in");
+    // (an evaluation without a log: it writes both bitmaps)
+    auto error_bitmap = [&](mxp_dbatch* db) -> int {
+        if ((e = de.reserve((size_t)J.W * n * 4)) != hipSuccess) return eng->hipfail(e, "alloc err");
+        if (int r = eng->launch(db, eng->stream, dm.as<uint32_t>(), de.as<uint32_t>(), nullptr, false)) return r;
+        A.err = de.as<uint32_t>();
+        J.pairs.on = false;
         return MXP_OK;
     };
-    if ((e = d_status.reserve(n)) != hipSuccess) return eng->hipfail(e, "alloc status");
-    if ((e = d_err_rule.reserve((size_t)n * 4)) != hipSuccess) return eng->hipfail(e, "alloc err_rule");
-    if ((e = d_count.reserve((size_t)n * 4)) != hipSuccess) return eng->hipfail(e, "alloc count");
-    const uint32_t grid = (n + 255u) / 256u;
-    if ((e = eng->res_bsum.reserve((size_t)grid * 8 + 8)) != hipSuccess) return eng->hipfail(e, "alloc block sums");
-    if ((e = d_off.reserve(((size_t)n + 1) * 8)) != hipSuccess) return eng->hipfail(e, "alloc sel_off");
-    if ((e = eng->res_stash.reserve((size_t)n * 16 + 16)) != hipSuccess) return eng->hipfail(e, "alloc stash");
-    mxp_resolve_args A;
-    memset(&A, 0, sizeof A);
-    A.n = n;
-    A.n_words = W;
-    A.nsinfo = d_info.as<uint32_t>();
-    A.ns_lo = d_lo.as<uint32_t>();
-    A.ns_hi = d_hi.as<uint32_t>();
-    A.default_id = R.default_id;
-    A.amask = d_amask.as<uint32_t>();
-    A.empty = d_empty.as<uint32_t>();
-    A.match = dm.as<uint32_t>();
-    A.err = compact ? nullptr : de.as<uint32_t>();
-    A.status = d_status.as<uint8_t>();
-    A.err_rule = d_err_rule.as<uint32_t>();
-    A.count = d_count.as<uint32_t>();
-    A.block_sum = eng->res_bsum.as<uint64_t>();
-    A.sel_off_out = d_off.as<uint64_t>();
-    A.sel_off = d_off.as<uint64_t>();
-    A.ids16 = ids16 ? 1u : 0u;
-    A.stash = (uint4*)eng->res_stash.p;
-    bool collected = false;  // (records collected after the resolve kernels unless a path needed them first)
-    if (compact) {
-        // the log's counts: [0] records, [2] class records (synchronises: the evaluation is done)
-        // (into pinned memory: both copies queued, one synchronisation)
-        if (!eng->res_small && (e = hipHostMalloc((void**)&eng->res_small, 64, hipHostMallocDefault)) != hipSuccess) {
-            eng->res_small = nullptr;
-            return eng->hipfail(e, "pinned counters");
-        }
-        uint32_t* const hs = eng->res_small;
-        hs[4] = hs[5] = 0;
-        if ((e = hipMemcpyAsync(hs, eng->d_errcount.p, 16, hipMemcpyDeviceToHost, eng->stream)) != hipSuccess ||
-            (J.pairs.on &&
-             (e = hipMemcpyAsync(hs + 4, J.pairs.ovf_n, 8, hipMemcpyDeviceToHost, eng->stream)) != hipSuccess) ||
-            (e = hipStreamSynchronize(eng->stream)) != hipSuccess)
-            return eng->hipfail(e, "download errcount");
-        const uint32_t cnt[4] = {hs[0], hs[1], hs[2], hs[3]}, ovf[2] = {hs[4], hs[5]};
-        // (pairs past their lists or slots: the fills stored the bitmap after all -- read it)
-        J.pairs_ovf = ovf[0];
-        J.recs_n = cnt[0];
-        J.class_recs_n = cnt[2];
-        if (ovf[0]) J.pairs.on = false;
-        if ((e = eng->res_err_in.reserve((size_t)n * 4 + 4)) != hipSuccess) return eng->hipfail(e, "alloc err_in");
-        if (n && (e = hipMemsetAsync(eng->res_err_in.p, 0xFF, (size_t)n * 4, eng->stream)) != hipSuccess)
-            return eng->hipfail(e, "reset err_in");
-        if (cnt[0] > eng->errcap) {
-            // records past the log's capacity: the error bitmap after all (an evaluation without a log)
-            if ((e = de.reserve((size_t)W * n * 4)) != hipSuccess) return eng->hipfail(e, "alloc err");
-            if ((rc = eng->launch(db.get(), eng->stream, dm.as<uint32_t>(), de.as<uint32_t>(), nullptr, false))) return rc;
-            A.err = de.as<uint32_t>();
-            J.pairs.on = false;  // (this evaluation wrote both bitmaps)
-            eng->trace_mark("error bitmap (log overflow)");
-        } else if (!cnt[2]) {
-            // each request's first error from the records, on the device
-            A.err_in = eng->res_err_in.as<uint32_t>();
-            A.err_rank = 1u;
-            if ((e = mxp_launch_resolve_first_err(&A, eng->d_errlog.p, cnt[0], eng->stream)) != hipSuccess)
-                return eng->hipfail(e, "launch first errors");
-            eng->trace_mark("first errors (device)");
+    if (n_recs > eng->errcap) {
+        // records past the log's capacity: the error bitmap after all
+        if ((rc = error_bitmap(J.db.get()))) return rc;
+        eng->trace_mark("error bitmap (log overflow)");
+    } else if (!n_class) {
+        // each request's first error from the records, on the device
+        A.err_in = eng->res_err_in.as<uint32_t>();
+        A.err_rank = 1u;
+        if ((e = mxp_launch_resolve_first_err(&A, eng->d_errlog.p, n_recs, eng->stream)) != hipSuccess)
+            return eng->hipfail(e, "launch first errors");
+        eng->trace_mark("first errors (device)");
+    } else {
+        // value-class records stand for whole classes: expanded per request on the host
+        // (collect_errors), then the first error of each failing request found there
+        if ((rc = eng->collect_errors(J.batch, J.db))) return rc;
+        *collected = true;
+        if (!eng->errors_complete) {
+            if ((rc = error_bitmap(eng->last_db.get()))) return rc;
         } else {
-            // value-class records stand for whole classes: expanded per request on the host
-            // (collect_errors), then the first error of each failing request found there
-            if ((rc = eng->collect_errors(batch, db))) return rc;
-            collected = true;
-            if (!eng->errors_complete) {
-                if ((e = de.reserve((size_t)W * n * 4)) != hipSuccess) return eng->hipfail(e, "alloc err");
-                if ((rc = eng->launch(eng->last_db.get(), eng->stream, dm.as<uint32_t>(), de.as<uint32_t>(), nullptr,
-                                      false)))
-                    return rc;
-                A.err = de.as<uint32_t>();
-                J.pairs.on = false;
-            } else {
-                if (n && hinfo == nullptr) {  // (the device namespaces, brought back for this pass)
-                    info.resize(n);
-                    if ((rc = eng->download(info.data(), d_info.p, (size_t)n * 4, "download nsinfo"))) return rc;
-                    hinfo = info.data();
-                }
-                std::vector<uint32_t> pairs;
-                first_errors(eng, n, variety, hinfo, &pairs);
-                if ((rc = up(eng->res_pairs, pairs.data(), pairs.size() * 4, "upload first errors"))) return rc;
-                if ((e = mxp_launch_resolve_scatter(eng->res_pairs.as<uint32_t>(), (uint32_t)(pairs.size() / 2),
-                                                    eng->res_err_in.as<uint32_t>(), eng->stream)) != hipSuccess)
-                    return eng->hipfail(e, "launch first errors");
-                A.err_in = eng->res_err_in.as<uint32_t>();
+            if (n && J.hinfo == nullptr) {  // (the device namespaces, brought back for this pass)
+                J.info.resize(n);
+                if ((rc = eng->download(J.info.data(), eng->res_info.p, (size_t)n * 4, "download nsinfo"))) return rc;
+                J.hinfo = J.info.data();
             }
-            eng->trace_mark("first errors (class records, host)");
+            std::vector<uint32_t> pairs;
+            first_errors(eng, n, J.variety, J.hinfo, &pairs);
+            if ((rc = upload(eng, eng->res_pairs, pairs.data(), pairs.size() * 4, "upload first errors"))) return rc;
+            if ((e = mxp_launch_resolve_scatter(eng->res_pairs.as<uint32_t>(), (uint32_t)(pairs.size() / 2),
+                                                eng->res_err_in.as<uint32_t>(), eng->stream)) != hipSuccess)
+                return eng->hipfail(e, "launch first errors");
+            A.err_in = eng->res_err_in.as<uint32_t>();
         }
+        eng->trace_mark("first errors (class records, host)");
     }
-    // (the default namespace's range tiled through LDS: resolve_tile; MXP_RESOLVE_TILE=0 the per-lane walk;
-    // a pair Resolve reads the filed pairs instead)
-    const bool tiled = eng->resolve_tile && R.default_id != MXP_NS_NONE;
+    return MXP_OK;
+}
+
+// Count and scan: the pass pair picked (the filed pairs where the evaluation left them and no error
+// bitmap is read; the default namespace's range tiled through LDS, resolve_tile, MXP_RESOLVE_TILE=0
+// the per-lane walk), its count pass and the scan launched.  *write_pass: the pair's write pass.
+int count_and_scan(mxp_resolve_job& J, mxp_resolve_args& A, ResPass* write_pass) {
+    mxp_engine* eng = J.eng;
+    const bool tiled = eng->resolve_tile && eng->resolver.default_id != MXP_NS_NONE;
     const bool pairs = J.pairs.on && !A.err;
-    if (eng->resolve_pairs == 2 && n && !pairs) {
+    if (eng->resolve_pairs == 2 && J.n && !pairs) {
         char why[160];
         snprintf(why, sizeof why,
                  "pair Resolve not taken (MXP_RESOLVE_PAIRS=2): pairs filed %d, overflowed %u, error bitmap %d "
@@ -474,130 +488,179 @@ int resolve_end(mxp_resolve_job& J, uint8_t* status, uint32_t* err_rule, uint64_
         A.pr_row = J.pairs.row;
         A.pr_nch = J.pairs.nch;
     }
-    const int count_mode = pairs ? 5 : tiled ? 3 : 0, write_mode = pairs ? 6 : tiled ? 4 : 1;
-    if (n && (e = mxp_launch_resolve(&A, count_mode, eng->stream)) != hipSuccess) return eng->hipfail(e, "launch resolve");
-    if (n && (e = mxp_launch_resolve(&A, 2, eng->stream)) != hipSuccess) return eng->hipfail(e, "launch resolve scan");
+    const ResPass count_pass = pairs ? kPairsCount : tiled ? kTileCount : kCount;
+    *write_pass = pairs ? kPairsWrite : tiled ? kTileWrite : kWrite;
+    hipError_t e;
+    if (J.n && (e = mxp_launch_resolve(&A, count_pass, eng->stream)) != hipSuccess) return eng->hipfail(e, "launch resolve");
+    if (J.n && (e = mxp_launch_resolve(&A, kScan, eng->stream)) != hipSuccess) return eng->hipfail(e, "launch resolve scan");
     eng->trace_mark("  resolve: count + scan kernels");
-    // The ids enqueued now, with the other outputs, when they go to the start of pinned caller memory:
-    // the write pass guarded by the capacity (it writes nothing past it) and a download sized on the
-    // device by sel_off[n] -- one synchronisation for every output instead of two (the ids' count is
-    // known on the host only after the first).  Otherwise, or when they do not fit, after it.
-    const size_t isz = d8 ? 1 : ids16 ? 2 : 4;  // (of a unit of sel_off / sel_cap: delta8 counts bytes)
-    const uint64_t early_cap = place ? J.first_cap : sel_cap;
-    // (delta8: a u16 scratch of early_cap entries beside the stream -- ids <= bytes, so it suffices
-    // whenever the stream fits; the encoder reads the list in 8-byte words: 16 bytes of slack)
-    void* const sel_hd = n && early_cap && !ref_off && early_cap * (d8 ? 3 : isz) <= kEarlyIdsMax
-                             ? eng->host_dev_ptr(sel_rules)
-                             : nullptr;
-    // delta8: the u16 list stays on the device (d_sel, id offsets d_off) and three encoder steps
-    // follow the write pass -- bytes per request (mxp_d8_count_kernel), their scan into byte offsets
-    // (the Resolve's scan kernels over a second argument block) and the stream (mxp_d8_write_kernel).
-    // The caller's sel_off receives the byte offsets.
-    DevBuf &d_boff = eng->res_boff, &d_d8 = eng->res_d8;
-    mxp_d8_args D;
-    mxp_resolve_args S;  // (the scan of the byte counts)
-    memset(&D, 0, sizeof D);
-    memset(&S, 0, sizeof S);
-    uint64_t* ids_total = nullptr;  // (pinned: the ids' count, with the first downloads)
-    if (d8) {
-        if ((e = eng->res_bcount.reserve((size_t)n * 4 + 4)) != hipSuccess) return eng->hipfail(e, "alloc byte counts");
-        if ((e = eng->res_bsum8.reserve((size_t)grid * 8 + 8)) != hipSuccess) return eng->hipfail(e, "alloc byte sums");
-        if ((e = d_boff.reserve(((size_t)n + 1) * 8)) != hipSuccess) return eng->hipfail(e, "alloc byte offsets");
-        if (!eng->res_small && (e = hipHostMalloc((void**)&eng->res_small, 64, hipHostMallocDefault)) != hipSuccess) {
-            eng->res_small = nullptr;
-            return eng->hipfail(e, "pinned counters");
-        }
-        ids_total = (uint64_t*)(eng->res_small + 8);
-        *ids_total = 0;
-        D.n = n;
-        D.id_off = d_off.as<uint64_t>();
+    return MXP_OK;
+}
+
+// The action lists' format, as the ids stage sees it.
+struct IdsFormat {
+    size_t unit;   // bytes of one unit of sel_off / sel_cap: an id, or for delta8 a byte of the stream
+    size_t id;     // bytes of an id as the write pass stores it
+    bool encoded;  // delta8: the u16 list stays on the device (res_sel, id offsets res_off) and the
+                   // encoder follows the write pass; the caller's sel_off receives byte offsets
+};
+IdsFormat ids_format(ResIds f) {
+    return f == ResIds::DELTA8 ? IdsFormat{1, 2, true} : f == ResIds::U16 ? IdsFormat{2, 2, false} : IdsFormat{4, 4, false};
+}
+
+// The ids stage: the action lists produced on the device (list, and for delta8 stream) and brought to
+// the caller (deliver_early / deliver_late).  A guard of 0 is no guard; under a guard a pass writes
+// nothing when its count exceeds it (the write pass: sel_off[n]; the encoder's passes: the ids, the
+// stream's also the bytes), so a guarded pass never writes past the room sized by that guard.
+struct IdsStage {
+    mxp_resolve_job& J;
+    mxp_resolve_args& A;
+    const ResPass write_pass;
+    const IdsFormat f;
+    ResSmall* small = nullptr;  // (encoded: ids_total, the ids' count, comes with the first downloads)
+    mxp_d8_args D{};            // encoded: bytes per request (mxp_d8_count_kernel), then the stream (mxp_d8_write_kernel)
+    mxp_resolve_args S{};       // ... and between them the Resolve's scan kernels over the byte counts
+
+    int init() {
+        if (!f.encoded) return MXP_OK;
+        mxp_engine* eng = J.eng;
+        const size_t n = J.n, grid = (J.n + 255u) / 256u;
+        hipError_t e;
+        if ((e = eng->res_bcount.reserve(n * 4 + 4)) != hipSuccess) return eng->hipfail(e, "alloc byte counts");
+        if ((e = eng->res_bsum8.reserve(grid * 8 + 8)) != hipSuccess) return eng->hipfail(e, "alloc byte sums");
+        if ((e = eng->res_boff.reserve((n + 1) * 8)) != hipSuccess) return eng->hipfail(e, "alloc byte offsets");
+        if (int rc = res_small(eng, &small)) return rc;
+        small->ids_total = 0;
+        D.n = J.n;
+        D.id_off = eng->res_off.as<uint64_t>();
         D.bcount = eng->res_bcount.as<uint32_t>();
         D.block_sum = eng->res_bsum8.as<uint64_t>();
-        D.boff = d_boff.as<uint64_t>();
-        S.n = n;
+        D.boff = eng->res_boff.as<uint64_t>();
+        S.n = J.n;
         S.count = D.bcount;
         S.block_sum = D.block_sum;
-        S.sel_off_out = d_boff.as<uint64_t>();
+        S.sel_off_out = eng->res_boff.as<uint64_t>();
+        return MXP_OK;
     }
-    // the u16 list in d_sel coded: byte offsets (cap: guarded, nothing when the ids exceed it) ...
-    auto d8_offsets = [&](uint64_t cap, uint32_t group) -> int {
+    // the device's copy of what the caller's sel_off receives
+    const uint64_t* offsets() const { return (f.encoded ? J.eng->res_boff : J.eng->res_off).as<uint64_t>(); }
+
+    // The ids into res_sel (room for `entries`), by the write pass; encoded: then their byte offsets
+    // (bytes per request and the scan).  group: the encoder's lanes per request.
+    int list(uint64_t entries, uint64_t guard, uint32_t group) {
+        mxp_engine* eng = J.eng;
+        DevBuf& d_sel = eng->res_sel;
+        // (the encoder reads the list in 8-byte words: 16 bytes of slack)
+        hipError_t e = d_sel.reserve(entries * f.id + (f.encoded ? 16 : 0));
+        if (e != hipSuccess) return eng->hipfail(e, "alloc sel");
+        A.sel_rules = d_sel.as<uint32_t>();
+        A.sel_cap_dev = guard;
+        if (entries) e = mxp_launch_resolve(&A, write_pass, eng->stream);
+        A.sel_cap_dev = 0;
+        if (e != hipSuccess) return eng->hipfail(e, "launch resolve write");
+        if (!f.encoded) return MXP_OK;
         D.ids = d_sel.as<uint16_t>();
-        D.cap = cap;
+        D.cap = guard;
         if ((e = mxp_launch_d8(&D, 0, group, eng->stream)) != hipSuccess ||
-            (e = mxp_launch_resolve(&S, 2, eng->stream)) != hipSuccess)
+            (e = mxp_launch_resolve(&S, kScan, eng->stream)) != hipSuccess)
             return eng->hipfail(e, "launch delta8 count");
         return MXP_OK;
-    };
-    // ... and the stream, into d_d8 (room for `room` bytes)
-    auto d8_stream = [&](uint64_t room, uint64_t cap, uint32_t group) -> int {
-        if ((e = d_d8.reserve(room)) != hipSuccess) return eng->hipfail(e, "alloc delta8 stream");
-        D.ids = d_sel.as<uint16_t>();
-        D.out = d_d8.as<uint8_t>();
-        D.cap = cap;
+    }
+    // encoded: the list in res_sel coded into res_d8 (room for `room` bytes)
+    int stream(uint64_t room, uint64_t guard, uint32_t group) {
+        mxp_engine* eng = J.eng;
+        hipError_t e;
+        if ((e = eng->res_d8.reserve(room)) != hipSuccess) return eng->hipfail(e, "alloc delta8 stream");
+        D.ids = eng->res_sel.as<uint16_t>();
+        D.out = eng->res_d8.as<uint8_t>();
+        D.cap = guard;
         if ((e = mxp_launch_d8(&D, 1, group, eng->stream)) != hipSuccess) return eng->hipfail(e, "launch delta8 write");
         return MXP_OK;
-    };
-    if (sel_hd && d8) {
-        // (the lanes per request from the capacity: the host does not know the ids' count yet, and a
-        // caller sizes the capacity by the lists it expects)
-        const uint32_t group = mxp_d8_group(early_cap / n);
-        if ((e = d_sel.reserve(early_cap * 2 + 16)) != hipSuccess) return eng->hipfail(e, "alloc sel");
-        A.sel_rules = d_sel.as<uint32_t>();
-        A.sel_cap_dev = early_cap;
-        if ((e = mxp_launch_resolve(&A, write_mode, eng->stream)) != hipSuccess) return eng->hipfail(e, "launch resolve write");
-        A.sel_cap_dev = 0;
-        if ((rc = d8_offsets(early_cap, group)) || (rc = d8_stream(early_cap, early_cap, group))) return rc;
-        if ((e = mxp_launch_d2h_copy_ids(sel_hd, d_d8.p, d_boff.as<uint64_t>() + n, 1u, early_cap, eng->stream)) !=
-            hipSuccess)
-            return eng->hipfail(e, "download sel");
-    } else if (sel_hd) {
-        if ((e = d_sel.reserve(early_cap * isz)) != hipSuccess) return eng->hipfail(e, "alloc sel");
-        A.sel_rules = d_sel.as<uint32_t>();
-        A.sel_cap_dev = early_cap;
-        if ((e = mxp_launch_resolve(&A, write_mode, eng->stream)) != hipSuccess) return eng->hipfail(e, "launch resolve write");
-        if ((e = mxp_launch_d2h_copy_ids(sel_hd, d_sel.p, d_off.as<uint64_t>() + n, (uint32_t)isz, early_cap,
-                                         eng->stream)) != hipSuccess)
-            return eng->hipfail(e, "download sel");
-        A.sel_cap_dev = 0;
+    }
+    const void* produced() const { return f.encoded ? J.eng->res_d8.p : J.eng->res_sel.p; }
+
+    // early: a copy kernel sized on the device by offsets()[n] into mapped pinned memory, nothing
+    // when that exceeds cap -- enqueued before the host knows the count
+    int deliver_early(void* sel_hd, uint64_t cap) {
+        const hipError_t e = mxp_launch_d2h_copy_ids(sel_hd, produced(), offsets() + J.n, (uint32_t)f.unit, cap, J.eng->stream);
+        return e == hipSuccess ? MXP_OK : J.eng->hipfail(e, "download sel");
+    }
+    // late: `total` units to unit `at` of the caller's list
+    int deliver_late(void* sel_rules, uint64_t at, uint64_t total) {
+        return J.eng->download((uint8_t*)sel_rules + (size_t)at * f.unit, produced(), total * f.unit, "download sel");
+    }
+};
+
+// The caller's sel_off from the device's offsets.  A group member (place != nullptr) never writes
+// sel_off[0]: that entry is the previous member's last one, and the group sets it.
+mxp_engine::Piece offsets_piece(uint64_t* sel_off, const uint64_t* offs, size_t n, bool member) {
+    return member ? mxp_engine::Piece{sel_off + 1, offs + 1, n * 8} : mxp_engine::Piece{sel_off, offs, (n + 1) * 8};
+}
+
+// The second phase, stage by stage.  On MXP_ERR_NOMEM status, err_rule and sel_off are complete:
+// every return of it comes after their downloads.
+int resolve_end(mxp_resolve_job& J, uint8_t* status, uint32_t* err_rule, uint64_t* sel_off, void* sel_rules,
+                uint64_t sel_cap, const mxp_resolve_place* place) {
+    mxp_engine* eng = J.eng;
+    const uint32_t n = J.n;
+    int rc;
+    mxp_resolve_args A;
+    if ((rc = resolve_args(J, &A))) return rc;
+    bool collected = false;  // (records collected after the resolve kernels unless the triage needed them first)
+    if (J.compact && (rc = triage_errors(J, A, &collected))) return rc;
+    ResPass write_pass;
+    if ((rc = count_and_scan(J, A, &write_pass))) return rc;
+    IdsStage ids{J, A, write_pass, ids_format(J.ids)};
+    if ((rc = ids.init())) return rc;
+    const IdsFormat& f = ids.f;
+    // The ids enqueued now, with the other outputs, when they go to the start of pinned caller memory:
+    // the passes guarded by the capacity and a copy sized on the device -- one synchronisation for
+    // every output instead of two (the ids' count is known on the host only after the first).
+    // Taken only when all of these hold: requests, a capacity, no referenced attributes, sel_rules a
+    // mapped pinned pointer, and the device buffers the capacity sizes (not the count; encoded: a u16
+    // list entry beside every stream byte, 3 bytes a unit) within kEarlyIdsMax.  A group member that
+    // is not the first has first_cap == 0, so it never goes early.
+    const uint64_t early_cap = place ? J.first_cap : sel_cap;
+    void* const sel_hd = n && early_cap && !J.ref_off && early_cap * (f.encoded ? f.id + f.unit : f.unit) <= kEarlyIdsMax
+                             ? eng->host_dev_ptr(sel_rules)
+                             : nullptr;
+    if (sel_hd) {
+        // encoded: the list's room is early_cap entries -- ids <= bytes, so it suffices whenever the
+        // stream fits; the lanes per request from early_cap / n (the host does not know the ids' count
+        // yet, and a caller sizes the capacity by the lists it expects)
+        const uint32_t group = f.encoded ? mxp_d8_group(early_cap / n) : 1u;
+        if ((rc = ids.list(early_cap, early_cap, group)) ||
+            (f.encoded && (rc = ids.stream(early_cap, early_cap, group))) || (rc = ids.deliver_early(sel_hd, early_cap)))
+            return rc;
     }
     if (!n) {
         if (!place) sel_off[0] = 0;
     } else {
-        // (delta8: the byte offsets, where the stream was enqueued above; else after the ids' count)
-        const uint64_t* const offs = d8 ? d_boff.as<uint64_t>() : d_off.as<uint64_t>();
-        std::vector<mxp_engine::Piece> outs = {{status, d_status.p, n}, {err_rule, d_err_rule.p, (size_t)n * 4}};
-        // (a group member leaves sel_off[0] alone: that entry is the previous member's last one)
-        if (!d8 || sel_hd)
-            outs.push_back(place ? mxp_engine::Piece{sel_off + 1, offs + 1, (size_t)n * 8}
-                                 : mxp_engine::Piece{sel_off, offs, ((size_t)n + 1) * 8});
-        if (d8) outs.push_back({ids_total, d_off.as<uint64_t>() + n, 8});
+        std::vector<mxp_engine::Piece> outs = {{status, eng->res_status.p, n}, {err_rule, eng->res_err_rule.p, (size_t)n * 4}};
+        // (encoded: the byte offsets only where the guarded passes above enqueued them)
+        if (!f.encoded || sel_hd) outs.push_back(offsets_piece(sel_off, ids.offsets(), n, place != nullptr));
+        if (f.encoded) outs.push_back({&ids.small->ids_total, eng->res_off.as<uint64_t>() + n, 8});
         if ((rc = eng->download_all(outs, "download resolve outputs"))) return rc;
     }
     eng->trace_mark("resolve kernels + downloads");
     if (!collected) {
-        if ((rc = eng->collect_errors(batch, db))) return rc;  // synchronises the stream
+        if ((rc = eng->collect_errors(J.batch, J.db))) return rc;  // synchronises the stream
         eng->trace_mark("error records");
     }
     int ref_rc = MXP_OK;
-    if (ref_off) {
-        const mxp_engine::RefScope scope{&info, status, err_rule, variety};
-        ref_rc = eng->refs_assemble(batch, recs, &scope, ref_off, refs, ref_cap);
+    if (J.ref_off) {
+        const mxp_engine::RefScope scope{&J.info, status, err_rule, J.variety};
+        ref_rc = eng->refs_assemble(J.batch, J.recs, &scope, J.ref_off, J.refs, J.ref_cap);
         if (ref_rc && ref_rc != MXP_ERR_NOMEM) return ref_rc;
     }
-    // delta8 after the first synchronisation: the ids' count is known.  Unless the guarded passes above
-    // ran with room for them (then the u16 list and the byte offsets stand), the u16 list is written
-    // now and its byte offsets computed and brought back.
-    const uint64_t ids_n = d8 && n ? *ids_total : 0;
-    const uint32_t d8_group = d8 && n ? mxp_d8_group((ids_n + n - 1) / n) : 1u;
-    if (d8 && n && !(sel_hd && ids_n <= early_cap)) {
-        if ((e = d_sel.reserve(ids_n * 2 + 16)) != hipSuccess) return eng->hipfail(e, "alloc sel");
-        A.sel_rules = d_sel.as<uint32_t>();
-        if (ids_n && (e = mxp_launch_resolve(&A, write_mode, eng->stream)) != hipSuccess)
-            return eng->hipfail(e, "launch resolve write");
-        if ((rc = d8_offsets(0, d8_group))) return rc;
-        if ((rc = eng->download_all({place ? mxp_engine::Piece{sel_off + 1, d_boff.as<uint64_t>() + 1, (size_t)n * 8}
-                                           : mxp_engine::Piece{sel_off, d_boff.p, ((size_t)n + 1) * 8}},
-                                    "download byte offsets")))
+    // encoded, after the first synchronisation: the ids' count is known, and the lanes per request
+    // come from the true mean.  The list is written again, and its byte offsets computed and brought
+    // back, only if the early list did not fit (or there was none): otherwise both stand.
+    const uint64_t ids_n = f.encoded && n ? ids.small->ids_total : 0;
+    const uint32_t group = f.encoded && n ? mxp_d8_group((ids_n + n - 1) / n) : 1u;
+    if (f.encoded && n && !(sel_hd && ids_n <= early_cap)) {
+        if ((rc = ids.list(ids_n, 0, group))) return rc;
+        if ((rc = eng->download_all({offsets_piece(sel_off, ids.offsets(), n, place != nullptr)}, "download byte offsets")))
             return rc;
         eng->trace_mark("delta8: u16 list + byte offsets");
     }
@@ -611,23 +674,18 @@ int resolve_end(mxp_resolve_job& J, uint8_t* status, uint32_t* err_rule, uint64_
     } else if (total > sel_cap) {
         return MXP_ERR_NOMEM;
     }
+    // the early result stands only if it fitted its guard and belongs at the start of the list
     if (total && sel_hd && total <= early_cap && at == 0) {
         eng->trace_mark("action lists (with the outputs)");
         return ref_rc;
     }
-    if (total && d8) {  // (the u16 list is in d_sel)
-        if ((rc = d8_stream(total, 0, d8_group))) return rc;
-        if ((rc = eng->download((uint8_t*)sel_rules + (size_t)at, d_d8.p, total, "download sel"))) return rc;
-    } else if (total) {
-        if ((e = d_sel.reserve(total * isz)) != hipSuccess) return eng->hipfail(e, "alloc sel");
-        A.sel_rules = d_sel.as<uint32_t>();
-        if ((e = mxp_launch_resolve(&A, write_mode, eng->stream)) != hipSuccess) return eng->hipfail(e, "launch resolve write");
-        if ((rc = eng->download((uint8_t*)sel_rules + (size_t)at * isz, d_sel.p, total * isz, "download sel"))) return rc;
+    if (total) {  // (encoded: the list is in res_sel by now -- the stream alone; else the write pass)
+        if ((rc = f.encoded ? ids.stream(total, 0, group) : ids.list(total, 0, group))) return rc;
+        if ((rc = ids.deliver_late(sel_rules, (uint64_t)at, total))) return rc;
     }
     eng->trace_mark("action lists (gather + download)");
     return ref_rc;
 }
-
 
 // mxp_resolve_batch(_ex), and with ref_off its referenced attributes (mxp_resolve_refs).
 //

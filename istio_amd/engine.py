@@ -304,6 +304,18 @@ def _ids_format(ids16: bool, delta8: bool):
     return flags, np.uint8 if delta8 else np.uint16 if ids16 else np.uint32
 
 
+def _resolve_outputs(n, cap, dtype, out=None, arena=None):
+    """A Resolve's (status u8[n], err_rule u32[n], sel_off u64[n + 1], sel_rules dtype[cap]): `out`
+    itself when its sel_rules holds cap, else new arrays -- from `arena` (a PinnedArena, started
+    over) or pageable."""
+    if out is not None and len(out[3]) >= cap:
+        return out
+    empty = np.empty
+    if arena is not None:
+        arena.used, empty = 0, arena.empty
+    return empty(n, np.uint8), empty(n, np.uint32), empty(n + 1, np.uint64), empty(max(cap, 1), dtype)
+
+
 def encode_delta8(off, ids):
     """The reference encoder of MXP_RESOLVE_IDS_DELTA8: (id offsets [n + 1], rule ids) -> (byte
     offsets u64[n + 1], stream u8).  Each request alone, prev = -1; per id d = id - prev - 1: one byte
@@ -661,28 +673,15 @@ class Engine:
         n = batch.n
         cap = cap or max(16, n * 4)
         flags, dt = _ids_format(ids16, delta8)
-        isz = dt().itemsize
-
-        def outputs(cap):
-            if not pinned:
-                return (np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint32), np.empty(n + 1, dtype=np.uint64),
-                        np.empty(cap, dtype=dt))
-            need = n * 13 + 8 + cap * isz + 4 * 64
-            if getattr(self, "_out_arena", None) is None or self._out_arena.size < need:
-                self._out_arena = PinnedArena(int(need * 1.25))
-            a = self._out_arena
-            a.used = 0
-            return (a.empty(n, np.uint8), a.empty(n, np.uint32), a.empty(n + 1, np.uint64),
-                    a.empty(cap, dt))
         for _ in range(2):
-            status, err_rule, off, sel = outputs(cap)
-            if flags:
-                rc = self.lib.mxp_resolve_batch_ex(self.h, ctypes.byref(batch.c_struct()), variety, flags,
-                                                   status.ctypes.data, err_rule.ctypes.data, off.ctypes.data,
-                                                   sel.ctypes.data, cap)
-            else:
-                rc = self.lib.mxp_resolve_batch(self.h, ctypes.byref(batch.c_struct()), variety, status.ctypes.data,
-                                                 err_rule.ctypes.data, off.ctypes.data, sel.ctypes.data, cap)
+            need = n * 13 + 8 + cap * dt().itemsize + 4 * 64
+            if pinned and (getattr(self, "_out_arena", None) is None or self._out_arena.size < need):
+                self._out_arena = PinnedArena(int(need * 1.25))
+            status, err_rule, off, sel = _resolve_outputs(n, cap, dt, arena=self._out_arena if pinned else None)
+            # (flags 0: mxp_resolve_batch itself)
+            rc = self.lib.mxp_resolve_batch_ex(self.h, ctypes.byref(batch.c_struct()), variety, flags,
+                                               status.ctypes.data, err_rule.ctypes.data, off.ctypes.data,
+                                               sel.ctypes.data, cap)
             if rc == 4:  # MXP_ERR_NOMEM: retry with the exact size
                 cap = int(off[n])
                 continue
@@ -695,8 +694,7 @@ class Engine:
         batch, cs = db._src
         n = batch.n
         flags, dt = _ids_format(ids16, delta8)
-        status, err_rule = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint32)
-        off, sel = np.empty(n + 1, dtype=np.uint64), np.empty(max(cap, 1), dtype=dt)
+        status, err_rule, off, sel = _resolve_outputs(n, cap, dt)
         h, db.h = db.h, None
         self._check(self.lib.mxp_resolve_uploaded(self.h, h, ctypes.byref(cs) if cs is not None else None, variety,
                                                   flags,
@@ -719,8 +717,7 @@ class Engine:
     def resolve_finish(self, job, cap: int):
         """mxp_resolve_finish -> (status, err_rule, sel_off, sel_rules) as resolve_uploaded."""
         h, n, dt, _src = job
-        status, err_rule = np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint32)
-        off, sel = np.empty(n + 1, dtype=np.uint64), np.empty(max(cap, 1), dtype=dt)
+        status, err_rule, off, sel = _resolve_outputs(n, cap, dt)
         self._check(self.lib.mxp_resolve_finish(h, status.ctypes.data, err_rule.ctypes.data, off.ctypes.data,
                                                 sel.ctypes.data, cap), "mxp_resolve_finish")
         return status, err_rule, off, sel[:int(off[n])]
@@ -1199,6 +1196,13 @@ class Group:
         arr = (_VP * len(cs))(*[ctypes.addressof(c) for c in cs])
         return cs, arr
 
+    @staticmethod
+    def _uploaded_shards(uploaded: "GroupBatch"):
+        """The pointer array of the very structs `uploaded`'s shards were uploaded from; None for narrow
+        uploads (the members keep the host views)."""
+        cs = uploaded._src[1]
+        return None if cs is None else (_VP * len(cs))(*[ctypes.addressof(c) for c in cs])
+
     def upload(self, shards: Sequence[BagBatch], no_wait: bool = False) -> "GroupBatch":
         """mxp_group_upload: shards[k] -> member k."""
         cs, arr = self._shards(shards)
@@ -1211,8 +1215,7 @@ class Group:
 
     def upload2(self, shards, no_wait: bool = False) -> "GroupBatch":
         """mxp_group_upload2: NarrowBatch shards (bags.py), member k's = shards[k]."""
-        cs = [b.c_struct() for b in shards]
-        arr = (_VP * len(cs))(*[ctypes.addressof(c) for c in cs])
+        cs, arr = self._shards(shards)
         h = _VP()
         self._check(self.lib.mxp_group_upload2(self.h, arr, len(cs), 1 if no_wait else 0, ctypes.byref(h)),
                     "mxp_group_upload2")
@@ -1279,24 +1282,13 @@ class Group:
         delta8: MXP_RESOLVE_IDS_DELTA8 (sel the u8 stream, sel_off and cap in bytes)."""
         n = sum(b.n for b in shards) if shards is not None else uploaded.n
         flags, dt = _ids_format(ids16, delta8)
-        if uploaded is None:
-            cs, arr = self._shards(shards)
-        elif uploaded._src[1] is None:  # (narrow uploads: the members keep the host views)
-            cs, arr = [None] * self.n, None
-        else:  # (the very structs the shards were uploaded from)
-            cs = uploaded._src[1]
-            arr = (_VP * len(cs))(*[ctypes.addressof(c) for c in cs])
+        cs, arr = self._shards(shards) if uploaded is None else (None, self._uploaded_shards(uploaded))
         cap = cap or max(16, n * 4)
         for _ in range(2):
-            if out is not None and len(out[3]) >= cap:
-                status, err_rule, off, sel = out
-            else:
-                status, err_rule, off = (np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint32),
-                                         np.empty(n + 1, dtype=np.uint64))
-                sel = np.empty(cap, dtype=dt)
+            status, err_rule, off, sel = _resolve_outputs(n, cap, dt, out)
             if uploaded is not None:
                 h, uploaded.h = uploaded.h, None
-                rc = self.lib.mxp_group_resolve_uploaded(self.h, h, arr, len(cs), variety, flags,
+                rc = self.lib.mxp_group_resolve_uploaded(self.h, h, arr, self.n, variety, flags,
                                                          status.ctypes.data, err_rule.ctypes.data, off.ctypes.data,
                                                          sel.ctypes.data, len(sel))
                 self._check(rc, "mxp_group_resolve_uploaded")
@@ -1314,11 +1306,7 @@ class Group:
     def resolve_submit(self, uploaded: "GroupBatch", variety: int, ids16: bool = False, delta8: bool = False):
         """mxp_group_resolve_submit: every member's evaluation of the uploaded shards enqueued (taken
         over) -> a job for resolve_finish; only an upload may come in between."""
-        if uploaded._src[1] is None:  # (narrow uploads: the members keep the host views)
-            arr = None
-        else:
-            cs = uploaded._src[1]
-            arr = (_VP * len(cs))(*[ctypes.addressof(c) for c in cs])
+        arr = self._uploaded_shards(uploaded)
         flags, dt = _ids_format(ids16, delta8)
         h, uploaded.h = uploaded.h, None
         job = _VP()
@@ -1329,12 +1317,7 @@ class Group:
     def resolve_finish(self, job, cap: int, out=None):
         """mxp_group_resolve_finish -> (status, err_rule, sel_off, sel_rules) of the whole batch."""
         h, n, dt, _src = job
-        if out is not None and len(out[3]) >= cap:
-            status, err_rule, off, sel = out
-        else:
-            status, err_rule, off = (np.empty(n, dtype=np.uint8), np.empty(n, dtype=np.uint32),
-                                     np.empty(n + 1, dtype=np.uint64))
-            sel = np.empty(max(cap, 1), dtype=dt)
+        status, err_rule, off, sel = _resolve_outputs(n, cap, dt, out)
         self._check(self.lib.mxp_group_resolve_finish(self.h, h, status.ctypes.data, err_rule.ctypes.data,
                                                       off.ctypes.data, sel.ctypes.data, len(sel)),
                     "mxp_group_resolve_finish")

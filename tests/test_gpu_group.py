@@ -11,7 +11,8 @@
   sequential restatement (oracle/memquota.py) does for the whole arrival stream, with the per-key
   deltas all-reduced into the counters.
 * Resolve, list checks and a finder vocabulary over the group equal the one-engine results.
-* A group larger than its batch (members with 0 or 1 requests) evaluates and resolves as one engine."""
+* A group larger than its batch (members with 0 or 1 requests) evaluates and resolves as one engine.
+* A capacity short of the batch's ids gives MXP_ERR_NOMEM with status, err_rule and sel_off complete."""
 import numpy as np
 import pytest
 
@@ -337,3 +338,78 @@ def test_group_members_with_few_or_no_requests(mxp, n):
     assert np.array_equal(e1[err], e2[err])
     eng.close()
     g.close()
+
+
+# ------------------------------------------------------------------ capacities short of the batch
+ERR_NOMEM = 4
+IDS_U16, IDS_DELTA8 = 1, 2
+
+
+@pytest.fixture(scope="module")
+def short_cap_case(mxp):
+    """A two-member group over c2_resolve_case(520, 2, 4096, seed=35), and per format what one engine
+    returns for the whole batch at variety 1 (delta8: its u16 lists through encode_delta8)."""
+    manifest, rules, conf, batch = W.c2_resolve_case(520, 2, 4096, seed=35)
+
+    def configured(x):
+        x.set_vocabulary(manifest)
+        x.compile(rules)
+        x.set_resolver(conf["identity_attr"], conf["default_ns"], conf["rule_ns"], conf["variety_mask"],
+                       conf["is_tcp"], conf["empty_match"])
+        return x
+    eng = configured(mxp.Engine(0))
+    st, er, off, ids = [x.copy() for x in eng.resolve_arrays(batch, 1, ids16=True)]
+    eng.close()
+    boff, stream = mxp.encode_delta8(off, ids)
+    g = configured(mxp.Group([0, 0]))
+    yield g, W.split_batch(batch, 2), {IDS_U16: (st, er, off, ids), IDS_DELTA8: (st, er, boff, stream)}
+    g.close()
+
+
+@pytest.mark.parametrize("pinned", [False, True], ids=["pageable", "pinned"])
+@pytest.mark.parametrize("flags", [IDS_U16, IDS_DELTA8], ids=["u16", "delta8"])
+def test_group_short_capacity(mxp, short_cap_case, flags, pinned):
+    """include/mxp_group.h: MXP_ERR_NOMEM when sel_cap is short, with status, err_rule and sel_off
+    complete -- mxp_group_resolve_batch and the submit / finish pair as called (no retry by the
+    mirror), capacities in the format's unit (ids, or bytes for delta8); the call again with
+    sel_off[n] then returns the ids."""
+    g, shards, wants = short_cap_case
+    want = wants[flags]
+    dt = want[3].dtype
+    n, total = len(want[0]), len(want[3])
+    assert total > 100 and (want[0] == 0).any() and (want[0] != 0).any()
+
+    def outputs(cap):
+        if not pinned:
+            return None, (np.empty(n, np.uint8), np.empty(n, np.uint32), np.empty(n + 1, np.uint64),
+                          np.empty(max(cap, 1), dt))
+        arena = mxp.PinnedArena(n * 13 + 8 + cap * dt.itemsize + 4 * 64)
+        return arena, (arena.empty(n, np.uint8), arena.empty(n, np.uint32), arena.empty(n + 1, np.uint64),
+                       arena.empty(cap, dt))
+
+    def batch_call(out, cap):
+        cs, arr = g._shards(shards)
+        return g.lib.mxp_group_resolve_batch(g.h, arr, len(cs), 1, flags, out[0].ctypes.data, out[1].ctypes.data,
+                                             out[2].ctypes.data, out[3].ctypes.data, cap)
+
+    def submit_finish(out, cap):
+        job = g.resolve_submit(g.upload(shards, no_wait=True), 1, ids16=flags == IDS_U16, delta8=flags == IDS_DELTA8)
+        return g.lib.mxp_group_resolve_finish(g.h, job[0], out[0].ctypes.data, out[1].ctypes.data, out[2].ctypes.data,
+                                              out[3].ctypes.data, cap)
+
+    for call in (batch_call, submit_finish):
+        for cap in (total, total - 1, 16):
+            what = (call.__name__, cap)
+            _keep, out = outputs(cap)
+            out[3][:] = 0
+            rc = call(out, cap)
+            assert rc == (0 if cap >= total else ERR_NOMEM), what
+            for name, x, y in zip(("status", "err_rule", "sel_off"), out, want):
+                assert np.array_equal(x, y), (what, name)
+            if rc:
+                cap = int(out[2][n])
+                _keep, out = outputs(cap)
+                assert call(out, cap) == 0, what
+                for name, x, y in zip(("status", "err_rule", "sel_off"), out, want):
+                    assert np.array_equal(x, y), (what, "retry", name)
+            assert np.array_equal(out[3][:total], want[3]), what

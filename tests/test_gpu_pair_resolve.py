@@ -14,7 +14,7 @@ import pytest
 import oracle
 import resolver as oracle_resolver
 from istio_amd import workloads as W
-from istio_amd.bags import ABSENT, STRING, BagBatch
+from istio_amd.workloads import c2_resolve_case
 
 pytestmark = pytest.mark.gpu
 
@@ -23,39 +23,6 @@ pytestmark = pytest.mark.gpu
 def mxp(libmxp):
     import istio_amd.engine as mxp
     return mxp
-
-
-def c2_resolve_case(n_base, copies, n_requests, seed):
-    """C2 requests over n_base C2 rules, plus a context.protocol column (tcp / http / missing) and 0.2 %
-    of the identities missing; the rule set is four namespace blocks in rule order ns1, ns0 (the
-    default), ns2, ns5 (the batch's destinations name ns0 .. ns7), each block the n_base rules
-    `copies` times over (copies n_base rules apart: a request matching one rule selects every copy
-    in both of its namespaces)."""
-    manifest, base, b = W.c2_workload(n_rules=n_base, n_requests=n_requests, seed=seed)
-    # (copy j compares source.ip with an address outside 10/8, where the requests' are: the same
-    # pairs, but a program of its own -- eight byte-identical rules would become a dense id)
-    block = [r.replace('ip("10.', 'ip("%d.' % (10 + j)) for j in range(copies) for r in base]
-    rules = block * 4
-    n_rules = len(rules)
-    rng = np.random.default_rng(seed + 7)
-    n = b.n
-    strings = [b.string(i) for i in range(b.n_strings)] + [b"tcp", b"http"]
-    offs = np.zeros(len(strings) + 1, dtype=np.uint64)
-    offs[1:] = np.cumsum([len(s) for s in strings])
-    blob = np.frombuffer(b"".join(strings) + b"\0", dtype=np.uint8).copy()
-    r = rng.random(n)
-    pk = np.where(r < 0.9, STRING, ABSENT).astype(np.uint8)
-    pv = np.where(r < 0.3, len(strings) - 2, len(strings) - 1).astype(np.uint64)
-    kinds = [k.copy() for k in b.kinds]
-    di = b.names.index("destination.service")
-    kinds[di][rng.random(n) < 0.002] = ABSENT  # (every rule errors there: few, so records fit the log)
-    batch = BagBatch(n, b.names + ["context.protocol"], kinds + [pk], b.values + [pv], blob, offs)
-    q = n_rules // 4
-    rule_ns = ["ns1"] * q + ["ns0"] * q + ["ns2"] * q + ["ns5"] * (n_rules - 3 * q)
-    conf = dict(rule_ns=rule_ns, variety_mask=[int(x) for x in rng.integers(1, 16, size=n_rules)],
-                is_tcp=[int(x) for x in rng.random(n_rules) < 0.3], empty_match=[0] * n_rules,
-                identity_attr="destination.service", default_ns="ns0")
-    return manifest, rules, conf, batch
 
 
 def engine_for(mxp, monkeypatch, manifest, rules, conf, pairs, extra=None):
