@@ -481,6 +481,12 @@ uint32_t mxp_dbatch_requests(const mxp_dbatch* db);
  * kernel launch, {start, end, XCC} (wall_clock64 ticks, 100 MHz), 3 x u64 per wave; *n_out = values
  * written.  MXP_ERR_STATE when the hook is off. */
 int mxp_debug_wave_times(mxp_engine* eng, uint64_t* out, uint64_t cap, uint64_t* n_out);
+/* Profiling hook: the deferred index pairs of the last device evaluation, which was a predicate
+ * evaluation of db -- {index waves, plain fill chunks, value-class fill chunks, wave list capacity},
+ * then each wave's list length (entries recorded, clamped to the capacity), downloaded after a
+ * device synchronisation; *n_out = values written (<= cap).  MXP_ERR_STATE when that evaluation
+ * deferred no pairs. */
+int mxp_debug_dtp_lists(mxp_engine* eng, const mxp_dbatch* db, uint32_t* out, uint64_t cap, uint64_t* n_out);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,7 @@
 //     (out[word * N + request]) so every store is a coalesced 256-byte wave store.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/mxp_batch.h"
 #include "kargs.h"
@@ -2026,30 +2027,46 @@ extern "C" __global__ __launch_bounds__(256) void mxp_dtp_sort_kernel(mxp_kargs 
     const uint32_t nwaves = (A.n + 63u) / 64u, w0 = t * 16u;
     const uint32_t nw = min(16u, nwaves - w0);
     const uint64_t nq = MXP_DTP_ROW(A.dtp_tiles);  // quads per chunk row
+    // The tile's (up to 16) wave lists as one range [0, ls[16]): ls[k] is where list k starts
+    // (wave-uniform running sums of the clamped lengths, read once).  Short lists (C2: a few dozen
+    // entries each) are then filed in one round of loads, long ones (C4: ~900) in four.
+    uint32_t ls[17];
+    ls[0] = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < 16u; k++) {
+        const uint32_t len = uni(A.dtp_n[min(w0 + k, nwaves - 1u)]);  // (clamped index: no branch per load)
+        ls[k + 1] = ls[k] + (k < nw ? min(len, A.dtp_cap) : 0u);
+    }
+    const uint32_t total = ls[16];
     for (uint32_t cw0 = 0; cw0 < A.dtp_nchunks; cw0 += MXP_DTP_WIN) {
         const uint32_t cwn = min(MXP_DTP_WIN, A.dtp_nchunks - cw0);
         for (uint32_t i = tid; i < cwn * 128u; i += 256u) cnt[i] = 0u;
         if (tid == 0) ovn = 0u;
         __syncthreads();
-        // four index waves' lists at a time, four entries of each per thread: 16 entries' loads (entry,
-        // then its chunk) in flight together (a list holds ~1k entries, so one step covers it)
-        for (uint32_t wb = 0; wb < nw; wb += 4u) {
-            uint32_t nl[4];
+        // U entries per thread and step, strided over the concatenated range: U entries' loads (entry,
+        // then its chunk) in flight together
+        auto step = [&](auto U_, uint32_t i0) {
+            constexpr uint32_t U = decltype(U_)::value;
+            uint32_t ev[U], cv[U], wv[U];
 #pragma unroll
-            for (uint32_t g = 0; g < 4u; g++) nl[g] = wb + g < nw ? min(uni(A.dtp_n[w0 + wb + g]), A.dtp_cap) : 0u;
-            const uint32_t nmax = max(max(nl[0], nl[1]), max(nl[2], nl[3]));
-            for (uint32_t i0 = tid; i0 < nmax; i0 += 1024u) {
-            uint32_t ev[16], cv[16];
+            for (uint32_t u = 0; u < U; u++) {
+                const uint32_t i = i0 + 256u * u;
+                // the list whose interval holds i (the last k with ls[k] <= i: empty lists are passed over)
+                uint32_t w = 0u, at = 0u;
 #pragma unroll
-            for (uint32_t u = 0; u < 16u; u++) {
-                const uint32_t g = u >> 2, i = i0 + 256u * (u & 3u);
-                ev[u] = i < nl[g] ? A.dtp_ent[(uint64_t)(w0 + wb + g) * A.dtp_cap + i] : 0xFFFFFFFFu;
+                for (uint32_t k = 1; k < 16u; k++) {
+                    const bool ge = i >= ls[k];
+                    w = ge ? k : w;
+                    at = ge ? ls[k] : at;
+                }
+                wv[u] = w;
+                ev[u] = i < total ? A.dtp_ent[(uint64_t)(w0 + w) * A.dtp_cap + (i - at)] : 0xFFFFFFFFu;
             }
 #pragma unroll
-            for (uint32_t u = 0; u < 16u; u++) cv[u] = ev[u] != 0xFFFFFFFFu ? A.dtp_chunk[(ev[u] & 0x7FFFFFu) >> 5] : 0u;
+            for (uint32_t u = 0; u < U; u++) cv[u] = ev[u] != 0xFFFFFFFFu ? A.dtp_chunk[(ev[u] & 0x7FFFFFu) >> 5] : 0u;
 #pragma unroll
-            for (uint32_t u = 0; u < 16u; u++) {
-                const uint32_t e = ev[u], w = wb + (u >> 2);
+            for (uint32_t u = 0; u < U; u++) {
+                const uint32_t e = ev[u], w = wv[u];
                 if (e == 0xFFFFFFFFu) continue;
                 const uint32_t rule = e & 0x7FFFFFu, ch = cv[u];
                 // fused hit counters (first window pass): a true pair into the workgroup's histogram
@@ -2078,13 +2095,24 @@ extern "C" __global__ __launch_bounds__(256) void mxp_dtp_sort_kernel(mxp_kargs 
                     }
                 }
             }
-            }
+        };
+        // (a C2 tile holds ~1k entries, 1.5k at most: one or two steps of 4 per thread, a quarter of
+        // the list searches of a step of 16; C4's ~14k take four steps of 16)
+        if (total <= 2048u) {
+            for (uint32_t i0 = tid; i0 < total; i0 += 1024u) step(std::integral_constant<uint32_t, 4u>{}, i0);
+        } else {
+            for (uint32_t i0 = tid; i0 < total; i0 += 4096u) step(std::integral_constant<uint32_t, 16u>{}, i0);
         }
         __syncthreads();
         if (hist && cw0 == 0)  // the tile's counts, summed over the tiles by mxp_dtp_hits_kernel
             for (uint32_t i = tid; i < R2; i += 256u) A.dtp_part[(uint64_t)t * R2 + i] = hc[i];
-        for (uint32_t i = tid; i < cwn * 256u; i += 256u)
-            A.dtp_qn[(uint64_t)(cw0 + (i >> 8)) * nq + t * 256u + (i & 255u)] = (uint8_t)min((cnt[i >> 1] >> ((i & 1u) << 4)) & 0xFFFFu, 8u);
+        // the quads' count bytes, four to a store (a chunk row and a tile's 256 bytes in it start on
+        // multiples of 8 and 256 bytes)
+        for (uint32_t i = tid; i < cwn * 64u; i += 256u) {
+            const uint32_t a = cnt[2u * i], b = cnt[2u * i + 1u];
+            const uint32_t k4 = min(a & 0xFFFFu, 8u) | min(a >> 16, 8u) << 8 | min(b & 0xFFFFu, 8u) << 16 | min(b >> 16, 8u) << 24;
+            *(uint32_t*)(A.dtp_qn + (uint64_t)(cw0 + (i >> 6)) * nq + t * 256u + (i & 63u) * 4u) = k4;
+        }
         const uint32_t no = min(ovn, MXP_DTP_OVQ);
         if (tid == 0 && no) ovbase = atomicAdd(&A.dtp_ovf_n[0], no);
         __syncthreads();

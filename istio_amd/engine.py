@@ -103,6 +103,7 @@ SIGNATURES = {
     "mxp_ruleset_columns": (ctypes.c_uint32, [_VP, ctypes.POINTER(ctypes.c_char_p), ctypes.c_uint32]),
     "mxp_debug_wave_times": (ctypes.c_int, [_VP, _VP, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     "mxp_debug_bin": (ctypes.c_int, [_VP, ctypes.POINTER(ctypes.c_uint64)]),
+    "mxp_debug_dtp_lists": (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]),
     "mxp_host_alloc": (ctypes.c_int, [ctypes.c_size_t, ctypes.POINTER(_VP)]),
     "mxp_host_free": (None, [_VP]),
     "mxp_go_to_upper": (ctypes.c_int, [ctypes.c_char_p, ctypes.c_uint64, _VP, ctypes.c_uint64,
@@ -816,6 +817,16 @@ class DeviceBatch:
         e = self.engine
         e._check(e.lib.mxp_batch_eval_device_hits(e.h, self.h, _VP(stream or None), _VP(d_match), _VP(d_err),
                                                   _VP(d_hits)), "mxp_batch_eval_device_hits")
+
+    def dtp_lists(self):
+        """Profiling hook (mxp_debug_dtp_lists), right after a device predicate evaluation of this
+        batch that deferred its index pairs: ({"waves", "fills", "vtfills", "cap"}, the wave lists'
+        lengths [waves])."""
+        e = self.engine
+        out = np.zeros(4 + (self.n + 63) // 64, dtype=np.uint32)
+        k = ctypes.c_uint64()
+        e._check(e.lib.mxp_debug_dtp_lists(e.h, self.h, out.ctypes.data, out.size, ctypes.byref(k)), "mxp_debug_dtp_lists")
+        return dict(zip(("waves", "fills", "vtfills", "cap"), out[:4].tolist())), out[4:k.value].copy()
 
     def eval_compact(self, d_match: int, d_req_err: int, d_hits: int = 0, stream: int = 0):
         """eval_hits() with compact error output: no error bitmap, d_req_err[q] (device u8) = 1 when some
