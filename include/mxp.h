@@ -439,6 +439,18 @@ int mxp_batch_eval_device_hits(mxp_engine* eng, mxp_dbatch* db, void* stream, ui
  * come from mxp_eval_batch / mxp_resolve_batch.  d_hits may be NULL (no counters). */
 int mxp_batch_eval_device_compact(mxp_engine* eng, mxp_dbatch* db, void* stream, uint32_t* d_match,
                                   uint8_t* d_req_err, unsigned long long* d_hits);
+/* A retained match bitmap.  The caller promises that from this call until the next mxp_match_retain
+ * on this engine only this engine's device evaluations write the `bytes` bytes at d_match (it may
+ * read them freely).  The engine then remembers what its last evaluation into d_match left there,
+ * and an evaluation whose words all come from plain fill chunks, with compact errors
+ * (mxp_batch_eval_device_compact) and the same request count as the one before it, rewrites only
+ * the 16-byte rows that held or hold a true pair instead of the whole bitmap.  Results
+ * are identical; evaluations into any other pointer are unaffected.  One retained buffer per engine:
+ * a call replaces it, (eng, NULL, 0) releases it, and every call makes the buffer's contents unknown
+ * to the engine (the next evaluation into it writes every word) -- so call it again after writing
+ * the buffer yourself or freeing and reallocating it.  MXP_FILL_RETAIN=0 (read at engine creation)
+ * turns the sparse rewrite off. */
+int mxp_match_retain(mxp_engine* eng, uint32_t* d_match, size_t bytes);
 /* Per-rule hit counters: d_hits[rule] += number of requests whose predicate was true (device u64[n_rules]). */
 int mxp_hits_device(mxp_engine* eng, const uint32_t* d_match, uint32_t n_requests, void* stream,
                     unsigned long long* d_hits);
@@ -457,7 +469,9 @@ int mxp_set_pipeline(mxp_engine* eng, uint32_t min_requests, uint32_t max_chunks
  * chunk (index kernels of all but the last chunk overlapped), [1] the exposed index tail.
  * Evaluations that deferred their index pairs into the fills ([2] = 1.0 when cap
  * >= 3): [0] value-class kernels + guard-index kernel + pair sort, [1] the fills, guard / VM
- * kernels and the overflow pass.  The sum is the whole evaluation.  *n_out = values written. */
+ * kernels and the overflow pass.  The sum is the whole evaluation.  [3] (cap >= 4) = 1.0 when the
+ * evaluation asked for a sparse fill of a retained bitmap (mxp_match_retain).  *n_out = values
+ * written. */
 int mxp_set_timing(mxp_engine* eng, int on);
 int mxp_kernel_times(mxp_engine* eng, float* ms, uint32_t cap, uint32_t* n_out);
 /* Shape of the compiled rule set as the kernels see it: out[0] guarded rules (leading atom evaluated
@@ -485,7 +499,12 @@ int mxp_debug_wave_times(mxp_engine* eng, uint64_t* out, uint64_t cap, uint64_t*
  * evaluation of db -- {index waves, plain fill chunks, value-class fill chunks, wave list capacity},
  * then each wave's list length (entries recorded, clamped to the capacity), downloaded after a
  * device synchronisation; *n_out = values written (<= cap).  MXP_ERR_STATE when that evaluation
- * deferred no pairs. */
+ * deferred no pairs.  With room for six more values after the lists (cap >= 4 + waves + 6), the
+ * retained-bitmap fill (mxp_match_retain): {1 when the launch asked for a sparse fill, the sparse
+ * fills so far that fell back to a dense one on the device (the previous overflow list was full),
+ * quad rows with pairs filed by this evaluation, by the previous one into the retained buffer (0
+ * unless sparse), this evaluation's quads with all 8 slots of a chunk taken, the pairs it sent to the
+ * overflow list}. */
 int mxp_debug_dtp_lists(mxp_engine* eng, const mxp_dbatch* db, uint32_t* out, uint64_t cap, uint64_t* n_out);
 
 #ifdef __cplusplus

@@ -1763,6 +1763,10 @@ int mxp_engine::launch(mxp_dbatch* db, hipStream_t s, uint32_t* d_match, uint32_
     if (db && db->pk_ev[3] && s != stream && (e = hipStreamWaitEvent(s, db->pk_ev[3], 0)) != hipSuccess)
         return hipfail(e, "wait for the packed batch");
     const int rc = launch_body(db, s, d_match, d_err, d_vals, log, d_hits, stats, q_lo, q_hi);
+    if (rc) {  // (part of it may have run: a retained bitmap and the overflow counters are unknown)
+        ret.valid = false;
+        dtp_dirty = true;
+    }
     if (db && db->note_done(s) != MXP_OK && !rc) return fail(MXP_ERR_DEVICE, "batch completion event");
     return rc;
 }
@@ -1773,6 +1777,12 @@ int mxp_engine::launch_body(mxp_dbatch* db, hipStream_t s, uint32_t* d_match, ui
     last_dtp = false;
     last_dtp_counted = false;
     last_pairs.on = false;
+    last_sparse = false;
+    // a retained match bitmap (mxp_match_retain): what it held before this launch; unknown from here
+    // until a launch that leaves it the OR of its filed pairs has been enqueued whole
+    const Retained held = ret;
+    const bool to_ret = ret.p && d_match == ret.p;
+    if (to_ret) ret.valid = false;
     // guards on: guard-only groups through the lean kernel, the rest through the VM kernel;
     // guards off (Eval, ablation): every group through the VM kernel
     const bool guards_on = !d_vals && !(debug_flags & 2u);
@@ -1938,40 +1948,53 @@ int mxp_engine::launch_body(mxp_dbatch* db, hipStream_t s, uint32_t* d_match, ui
             dtp_ev = nullptr;
             return hipfail(e, "deferred-pair event");
         }
+        // the filed pairs go to the scratch generation that does not hold a retained bitmap's pairs
+        // (an interleaved Resolve or an evaluation into another buffer leaves those readable)
+        const uint32_t gen = held.valid ? held.gen ^ 1u : 0u;
+        DevBuf &g_ovf = d_dtp_ovf[gen], &g_slots = d_dtp_slots[gen], &g_qn = d_dtp_qn[gen];
         if (dtp_pending) {
             if (dtp_stream != s && (e = hipStreamWaitEvent(s, dtp_ev, 0)) != hipSuccess) return hipfail(e, "deferred-pair wait");
             const size_t need_slots = (size_t)(P->n_fills + P->n_vtfills) * MXP_DTP_ROW(tiles) * 16;
-            if ((d_dtp_ent.n < (size_t)cx * dtp_cap * 4 || d_dtp_n.n < (size_t)grid * 16 || d_dtp_slots.n < need_slots ||
-                 d_dtp_qn.n < need_slots / 16 || d_dtp_ovf.n < (size_t)dtp_ovf_cap * 8 ||
+            if ((d_dtp_ent.n < (size_t)cx * dtp_cap * 4 || d_dtp_n.n < (size_t)grid * 16 || g_slots.n < need_slots ||
+                 g_qn.n < need_slots / 16 || g_ovf.n < (size_t)dtp_ovf_cap * 8 ||
                  (dtp_count && d_dtp_part.n < (size_t)tiles * ((A.n_rules + 1) / 2) * 4)) &&
                 (e = hipEventSynchronize(dtp_ev)) != hipSuccess)
                 return hipfail(e, "deferred-pair sync");
         }
         if ((e = d_dtp_ent.reserve((size_t)cx * dtp_cap * 4)) != hipSuccess ||
             (e = d_dtp_n.reserve((size_t)grid * 4 * 4)) != hipSuccess ||
-            (e = d_dtp_ovf.reserve((size_t)dtp_ovf_cap * 8)) != hipSuccess ||
-            (e = d_dtp_slots.reserve((size_t)(P->n_fills + P->n_vtfills) * MXP_DTP_ROW(tiles) * 16)) != hipSuccess ||
-            (e = d_dtp_qn.reserve((size_t)(P->n_fills + P->n_vtfills) * MXP_DTP_ROW(tiles))) != hipSuccess)
+            (e = g_ovf.reserve((size_t)dtp_ovf_cap * 8)) != hipSuccess ||
+            (e = g_slots.reserve((size_t)(P->n_fills + P->n_vtfills) * MXP_DTP_ROW(tiles) * 16)) != hipSuccess ||
+            (e = g_qn.reserve((size_t)(P->n_fills + P->n_vtfills) * MXP_DTP_ROW(tiles))) != hipSuccess)
             return hipfail(e, "deferred-pair scratch");
-        if (!d_dtp_ovf_n.p) {  // two counter sets (count, list full): each launch's sort kernel resets the other
-            if ((e = d_dtp_ovf_n.alloc(32)) != hipSuccess) return hipfail(e, "deferred-pair counters");
-            if ((e = hipMemsetAsync(d_dtp_ovf_n.p, 0, 32, s)) != hipSuccess) return hipfail(e, "memset dtp");
+        // three counter sets (count, list full): a launch's sort kernel resets the set the next launch
+        // uses -- never its own, never the set of a retained bitmap's evaluation
+        if (!d_dtp_ovf_n.p) {
+            if ((e = d_dtp_ovf_n.alloc(48)) != hipSuccess) return hipfail(e, "deferred-pair counters");
+            dtp_dirty = true;
         }
-        uint32_t* const ovf_n = d_dtp_ovf_n.as<uint32_t>() + 4u * dtp_par;
-        uint32_t* const ovf_next = d_dtp_ovf_n.as<uint32_t>() + 4u * (dtp_par ^ 1u);
-        dtp_par ^= 1u;
+        if (dtp_dirty) {
+            if ((e = hipMemsetAsync(d_dtp_ovf_n.p, 0, 48, s)) != hipSuccess) return hipfail(e, "memset dtp");
+            dtp_dirty = false;
+        }
+        const uint32_t cset = dtp_cset;
+        uint32_t cnext = (cset + 1u) % 3u;
+        if (held.valid && cnext == held.cset) cnext = (cnext + 1u) % 3u;
+        uint32_t* const ovf_n = d_dtp_ovf_n.as<uint32_t>() + 4u * cset;
+        uint32_t* const ovf_next = d_dtp_ovf_n.as<uint32_t>() + 4u * cnext;
+        dtp_cset = cnext;
         mxp_kargs AI = A;  // the index kernel records
         AI.req_err_init = A.req_err ? 1u : 0u;
         AI.dtp_ent = d_dtp_ent.as<uint32_t>();
         AI.dtp_n = d_dtp_n.as<uint32_t>();
         AI.dtp_ovf_n = ovf_n;
         AI.dtp_ovf_next = ovf_next;
-        AI.dtp_ovf = d_dtp_ovf.as<uint32_t>();
+        AI.dtp_ovf = g_ovf.as<uint32_t>();
         AI.dtp_cap = dtp_cap;
         AI.dtp_ovf_cap = dtp_ovf_cap;
         AI.dtp_chunk = P->d_dtp_chunk.as<uint32_t>();
-        AI.dtp_slots = d_dtp_slots.as<uint16_t>();
-        AI.dtp_qn = d_dtp_qn.as<uint8_t>();
+        AI.dtp_slots = g_slots.as<uint16_t>();
+        AI.dtp_qn = g_qn.as<uint8_t>();
         AI.dtp_tiles = tiles;
         AI.dtp_nchunks = P->n_fills + P->n_vtfills;
         if (dtp_count) {
@@ -2009,8 +2032,31 @@ int mxp_engine::launch_body(mxp_dbatch* db, hipStream_t s, uint32_t* d_match, ui
         // a pair Resolve's evaluation: every word a plain fill chunk's (no lean / VM / deep groups, no
         // value classes), so the filed pairs are the match bitmap -- the fills store it only if some
         // pair overflowed its list or slots (kargs.dtp_lazy)
-        if (pair_req && P->n_fills && !P->n_vtfills && !P->n_glean && !P->n_gvm && !P->n_gdeep && !A.n_vt &&
-            !A.out_err) {
+        const bool plain = P->n_fills && !P->n_vtfills && !P->n_glean && !P->n_gvm && !P->n_gdeep && !A.n_vt && !A.out_err;
+        // ... and for the same reason an evaluation into a retained bitmap leaves it the OR of the
+        // pairs filed here (`keeps`); if the bitmap still holds the previous such evaluation's, in
+        // the same geometry, the fills store only the rows either of the two names (kargs.ret_w)
+        const bool keeps = to_ret && fill_retain && plain && !pair_req && K == 1 &&
+                           (uint64_t)A.n_words * A.n * 4u <= held.bytes;
+        const bool sparse = keeps && held.valid && held.n == A.n && held.tiles == tiles && held.plan == P;
+        if (sparse) {
+            if (!d_ret_w.p) {
+                if ((e = d_ret_w.alloc(16)) != hipSuccess) return hipfail(e, "retained-bitmap words");
+                if ((e = hipMemsetAsync(d_ret_w.p, 0, 16, s)) != hipSuccess) return hipfail(e, "memset retained-bitmap words");
+            }
+            AI.ret_w = AF.ret_w = d_ret_w.as<uint32_t>();
+            AI.dtp_povf = d_dtp_ovf[held.gen].as<uint32_t>();
+            AI.dtp_povf_n = d_dtp_ovf_n.as<uint32_t>() + 4u * held.cset;
+            AF.dtp_pslots = d_dtp_slots[held.gen].as<uint16_t>();
+            AF.dtp_pqn = d_dtp_qn[held.gen].as<uint8_t>();
+        }
+        last_sparse = sparse;
+        last_gen = gen;
+        last_cset = cset;
+        last_prev_gen = held.gen;
+        last_tiles = tiles;
+        last_nch = P->n_fills + P->n_vtfills;
+        if (pair_req && plain) {
             AF.dtp_lazy = ovf_n;
             last_pairs.on = true;
             last_pairs.ovf_n = ovf_n;
@@ -2068,6 +2114,14 @@ int mxp_engine::launch_body(mxp_dbatch* db, hipStream_t s, uint32_t* d_match, ui
         if ((e = hipEventRecord(dtp_ev, s)) != hipSuccess) return hipfail(e, "deferred-pair event");
         dtp_pending = true;
         dtp_stream = s;
+        if (keeps) {  // the retained bitmap now holds this launch's pairs
+            ret.valid = true;
+            ret.n = A.n;
+            ret.tiles = tiles;
+            ret.plan = P;
+            ret.gen = gen;
+            ret.cset = cset;
+        }
         if (timing && (e = hipEventRecord(ev[2], s)) != hipSuccess) return hipfail(e, "event");
         ev_index = true;
         last_mask = mask;
@@ -2260,6 +2314,7 @@ int mxp_engine_create(int device, mxp_engine** out) {
     if (const char* f = getenv("MXP_DTP")) e->dtp = atoi(f) != 0;
     if (const char* f = getenv("MXP_DTP_CAP")) e->dtp_cap = (uint32_t)std::min(1 << 20, std::max(1, atoi(f)));
     if (const char* f = getenv("MXP_DTP_OVF")) e->dtp_ovf_cap = (uint32_t)std::max(1, atoi(f));
+    if (const char* f = getenv("MXP_FILL_RETAIN")) e->fill_retain = atoi(f) != 0;
     if (const char* f = getenv("MXP_INDEX_SPARSITY")) e->index_sparsity = (uint32_t)std::min(8, std::max(0, atoi(f)));
     // tuning knobs (results are identical for every setting)
     if (const char* f = getenv("MXP_GPW")) e->groups_per_wave = std::max(1, atoi(f));
@@ -2408,6 +2463,14 @@ int mxp_set_timing(mxp_engine* eng, int on) {
     return MXP_OK;
 }
 
+int mxp_match_retain(mxp_engine* eng, uint32_t* d_match, size_t bytes) {
+    if (!eng || (!d_match) != (bytes == 0)) return MXP_ERR_ARG;
+    eng->ret = mxp_engine::Retained();  // (whatever the engine knew about a retained buffer is void)
+    eng->ret.p = d_match;
+    eng->ret.bytes = bytes;
+    return MXP_OK;
+}
+
 int mxp_kernel_times(mxp_engine* eng, float* ms, uint32_t cap, uint32_t* n_out) {
     if (!eng || !ms || !n_out) return MXP_ERR_ARG;
     *n_out = 0;
@@ -2418,9 +2481,9 @@ int mxp_kernel_times(mxp_engine* eng, float* ms, uint32_t cap, uint32_t* n_out) 
     if ((e = hipEventElapsedTime(&t[0], eng->ev[0], eng->ev[1])) != hipSuccess) return eng->hipfail(e, "elapsed");
     if ((e = hipEventElapsedTime(&t[1], eng->ev[1], eng->ev[2])) != hipSuccess)
         return eng->hipfail(e, "elapsed");
-    const float tt[3] = {t[0], t[1], eng->last_dtp ? 1.f : 0.f};
+    const float tt[4] = {t[0], t[1], eng->last_dtp ? 1.f : 0.f, eng->last_sparse ? 1.f : 0.f};
     uint32_t k = 0;
-    for (; k < cap && k < 3; k++) ms[k] = tt[k];
+    for (; k < cap && k < 4; k++) ms[k] = tt[k];
     *n_out = k;
     return MXP_OK;
 }

@@ -155,6 +155,7 @@ struct DevBuf {
     void* p = nullptr;
     size_t n = 0;    // bytes asked for
     size_t cap = 0;  // bytes the block holds (>= n: a recycled block may be larger)
+    uint64_t allocs = 0;  // alloc() calls so far: a change means another block, whatever its address
     DevBuf() = default;
     DevBuf(const DevBuf&) = delete;
     DevBuf& operator=(const DevBuf&) = delete;
@@ -178,6 +179,7 @@ struct DevBuf {
     }
     hipError_t alloc(size_t bytes) {
         reset();
+        allocs++;
         if (bytes == 0) bytes = 16;
         n = bytes;
         if (in_batch() && g_bin_take->take(bytes, &p, &cap)) return hipSuccess;
@@ -554,7 +556,8 @@ struct mxp_engine : public mxp::LowerTables {
     // 16 no composite index, 64 no duplicate folding, 128 plain fill stores, 256 no dense injection,
     // 512 index equality-only guards too, 524288 / 1048576 fused / streaming hit counters forced,
     // 2097152 value-class fill chunks gather from global memory (no LDS staging), 16384 long posting
-    // lists of the guard index walked by their own lane (no wave-cooperative expansion; same results)
+    // lists of the guard index walked by their own lane (no wave-cooperative expansion; same results),
+    // 4194304 non-temporal row stores in the retained-bitmap fill
     // fill layout (same-box A/B on C2, profiles/r1_v17_ab_fill*.log: span 1 / chunk 32 0.945 ms,
     // span 4 0.832-0.836, span 4 / chunk 16 0.831; spans 3, 5, 6, 8 and chunks 4..1000 no better)
     uint32_t fill_chunk = MXP_FILL_CHUNK;  // MXP_FILL_CHUNK: groups per fill chunk
@@ -576,7 +579,29 @@ struct mxp_engine : public mxp::LowerTables {
     // on aliased HBM channels: C4 0.745 -> 0.710 ms, the path-only routes 0.630 -> 0.618 ms with 2080,
     // settings alternated in one process, profiles/r4_s3{3,4,5}_ab_*_dtpcap.log)
     uint32_t dtp_cap = 2080, dtp_ovf_cap = 1u << 22;
-    DevBuf d_dtp_ent, d_dtp_n, d_dtp_ovf, d_dtp_ovf_n, d_dtp_slots, d_dtp_qn;
+    // (the filed pairs -- overflow list, slot rows, count bytes -- in two generations: a launch writes
+    // the one that does not hold a retained bitmap's pairs; the second is allocated at its first use)
+    DevBuf d_dtp_ent, d_dtp_n, d_dtp_ovf[2], d_dtp_ovf_n, d_dtp_slots[2], d_dtp_qn[2];
+    // Retained match bitmap (mxp_match_retain): until the caller releases it only this
+    // engine's evaluations write the buffer, so an all-plain-fill deferred evaluation into it leaves
+    // exactly the OR of the pairs it filed, and the next such evaluation stores only the quad rows
+    // that held a pair then or hold one now (kargs.ret_w).  The record says what the buffer holds;
+    // anything else written into it, a failed launch, a new rule set or vocabulary make it unknown.
+    // MXP_FILL_RETAIN=0: every fill dense.
+    bool fill_retain = true;
+    struct Retained {
+        uint32_t* p = nullptr;
+        size_t bytes = 0;
+        bool valid = false;          // the fields below describe the buffer's contents
+        uint32_t n = 0, tiles = 0;   // pitch (requests) and sort tiles of that evaluation
+        const Plan* plan = nullptr;  // (plans die with the rule set: reset_tables)
+        uint32_t gen = 0, cset = 0;  // scratch generation and overflow-counter set of its pairs
+    } ret;
+    DevBuf d_ret_w;                  // kargs.ret_w: {this launch fills densely, dense fallbacks so far}
+    // mxp_debug_dtp_lists: the last deferred launch asked for a sparse fill; its scratch generation
+    // and chunk-row geometry, the previous one's when sparse
+    bool last_sparse = false;
+    uint32_t last_gen = 0, last_prev_gen = 0, last_tiles = 0, last_nch = 0, last_cset = 0;
     bool last_dtp = false;  // the last launch deferred its index pairs (mxp_kernel_times [2])
     bool last_dtp_counted = false;  // ... and counted every true pair in its kernels (no streamed counters)
     // pair Resolve (resolver.cpp): the resolver asks (pair_req) that the next evaluation leave the match
@@ -595,7 +620,10 @@ struct mxp_engine : public mxp::LowerTables {
     } last_pairs;
     static constexpr uint32_t kDtpHist = 16384;  // MXP_DTP_HIST (kernels.hip): rule sets counted by histogram
     DevBuf d_dtp_part;                // [tiles][(R + 1) / 2] per-tile true-pair histograms
-    uint32_t dtp_par = 0;   // d_dtp_ovf_n holds two counter sets: this launch's and the next one's
+    // d_dtp_ovf_n holds three counter sets: this launch's, the next one's (reset by this launch's
+    // sort kernel) and the one a retained bitmap's evaluation left, which stays readable
+    uint32_t dtp_cset = 0;
+    bool dtp_dirty = false;  // a launch failed part-way: the counters are cleared before the next one
     hipEvent_t dtp_ev = nullptr;      // recorded after each deferred launch (its last kernel)
     hipStream_t dtp_stream = nullptr; // ... on this stream; a launch on another stream waits for it
     bool dtp_pending = false;
@@ -810,6 +838,7 @@ struct mxp_engine : public mxp::LowerTables {
     }
 
     void reset_tables() {
+        ret.valid = false;  // (a retained bitmap's record belongs to the old rule set's plans)
         resolver = ResolverConf();  // a new rule set needs a new resolver configuration
         gstr_ids.clear();
         gstrs.clear();

@@ -179,6 +179,7 @@ struct mxp_group {
         DevBuf match, err, req_err;    // results of the last mxp_group_eval
         uint32_t eval_n = 0;
         bool eval_bitmap = false, evaluated = false;
+        bool retained = false;         // match is the engine's retained bitmap (mxp_match_retain)
         hipStream_t qs = nullptr;      // memquota stream (beside the evaluation)
         // the member's evaluation stream: non-blocking, so the engine's synchronous copies on the
         // legacy stream (a batch upload's, a pack's) never wait for a queued evaluation
@@ -729,7 +730,20 @@ int mxp_group_eval(mxp_group* g, mxp_gbatch* gb, uint32_t flags) {
         x.evaluated = true;
         if (!n) return MXP_OK;
         hipError_t e;
-        if ((e = x.match.reserve(W * n * 4)) != hipSuccess) return x.eng->hipfail(e, "alloc match bitmap");
+        // the member's bitmap is retained for its engine (mxp_match_retain: nobody else writes it, so
+        // a compact evaluation rewrites only the rows that change); a new block -- possibly at the
+        // old address, with other contents -- is retained afresh, its contents unknown.  The
+        // error-bitmap form writes it densely and leaves it unknown to the engine.
+        const uint64_t allocs = x.match.allocs;
+        if ((e = x.match.reserve(W * n * 4)) != hipSuccess) {
+            (void)mxp_match_retain(x.eng, nullptr, 0);
+            x.retained = false;
+            return x.eng->hipfail(e, "alloc match bitmap");
+        }
+        if ((!x.retained || x.match.allocs != allocs) &&
+            mxp_match_retain(x.eng, x.match.as<uint32_t>(), x.match.cap) != MXP_OK)
+            return MXP_ERR_ARG;
+        x.retained = true;
         unsigned long long* hits = (unsigned long long*)x.step.p;
         if (bitmap) {
             if ((e = x.err.reserve(W * n * 4)) != hipSuccess) return x.eng->hipfail(e, "alloc error bitmap");

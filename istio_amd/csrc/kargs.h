@@ -151,6 +151,18 @@ typedef struct mxp_kargs {
     // this evaluation's deferred pairs overflowed (*dtp_lazy, its dtp_ovf_n[0], nonzero) -- otherwise
     // the Resolve reads the filed pairs themselves and the match bitmap is never written (null: store)
     const uint32_t* dtp_lazy;
+    // A retained match bitmap (mxp_match_retain, DESIGN.md §4 "Retained match bitmap"): the buffer
+    // still holds what the previous evaluation into it wrote -- the OR of that evaluation's filed
+    // match-plane pairs (dtp_pslots / dtp_pqn, the other scratch generation) and of its overflow list
+    // (dtp_povf, dtp_povf_n).  mxp_dtp_sort_kernel clears the previous overflow pairs' bits and
+    // writes ret_w[0] (1: that list was full, its re-run OR-ed pairs nobody recorded -- fill densely;
+    // ret_w[1] counts those fallbacks); mxp_fill_dtp_kernel then stores only the quad rows that held a
+    // match-plane pair then or hold one now (null ret_w: every row, as always).
+    uint32_t* ret_w;
+    const uint16_t* dtp_pslots;
+    const uint8_t* dtp_pqn;
+    const uint32_t* dtp_povf;
+    const uint32_t* dtp_povf_n;
 } mxp_kargs;
 
 // mxp_vtd_final_kernel: the packer's provisional class tables and the candidate column of each

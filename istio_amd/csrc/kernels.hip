@@ -1364,6 +1364,42 @@ struct DtpQueue {
         const v4u sl = *(const v4u*)(A.dtp_slots + qi * 8u);
         decode(dk, sl);
     }
+    // load() from either scratch generation (the retained-bitmap fill), the row only behind a nonzero
+    // count: most quads are empty, and their rows are never read
+    __device__ __forceinline__ void load_live(const uint16_t* slots, const uint8_t* qn, uint32_t tiles, uint32_t chunk,
+                                              uint32_t req0, bool in) {
+        if (!in) return;
+        typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+        const uint64_t qi = (uint64_t)chunk * MXP_DTP_ROW(tiles) + (req0 >> 2);
+        const uint32_t dk = qn[qi];
+        if (!dk) return;
+        const v4u sl = *(const v4u*)(slots + qi * 8u);
+        decode(dk, sl);
+    }
+    // The retained-bitmap fill walks a lane's own queue (no wave-wide group loop: a C2 wave's 64
+    // quads hold a dozen pairs between them, in one or two of the chunk's groups each).
+    // The group the head entry names, 256 when the queue is empty:
+    __device__ __forceinline__ uint32_t head_group() const { return (q0 & 0xFFFFu) == 0xFFFFu ? 256u : (q0 >> 8) & 0xFFu; }
+    // the head entries naming group g OR-ed into m, match plane only; whether a match-plane entry
+    // named it.  (Error-plane entries would be consumed and touch nothing.  That is defensive: both
+    // evaluations of a sparse fill ran without an error bitmap, and such an index kernel files no
+    // error pair.)
+    __device__ __forceinline__ bool take(uint32_t g, uint32_t (&m)[4]) {
+        bool named = false;
+        while (head_group() == g) {
+            const uint32_t x = q0 & 0xFFFFu;
+            const bool mp = !(x & 128u);
+            const uint32_t b = mp ? 1u << (x & 31u) : 0u, r = (x >> 5) & 3u;
+#pragma unroll
+            for (uint32_t k = 0; k < 4; k++) m[k] |= r == k ? b : 0u;
+            named |= mp;
+            q0 = __builtin_amdgcn_alignbit(q1, q0, 16);
+            q1 = __builtin_amdgcn_alignbit(q2, q1, 16);
+            q2 = __builtin_amdgcn_alignbit(q3, q2, 16);
+            q3 = q3 >> 16 | 0xFFFF0000u;
+        }
+        return named;
+    }
     // the sorted queue from a quad's raw count and slot row (load, or a prefetch of them)
     template <typename V4>
     __device__ __forceinline__ void decode(uint32_t dk, const V4& sl) {
@@ -1607,8 +1643,16 @@ extern "C" __global__ __launch_bounds__(256) void mxp_fill_dtp_kernel(mxp_kargs 
     const bool any = (bad[0] | bad[1] | bad[2] | bad[3]) != 0;
     // (a pair Resolve's evaluation: only the request error flags and records unless pairs overflowed)
     const bool store = !A.dtp_lazy || uni(*A.dtp_lazy) != 0u;
-    DtpQueue dq;
-    if (store) dq.load(A, A.dtp_cbase + blockIdx.y, q0, q0 < Q1);
+    // (a retained bitmap that still holds the previous evaluation's pairs, kargs.ret_w: only the rows
+    // either evaluation names -- unless mxp_dtp_sort_kernel found the previous overflow list full)
+    const bool sparse = A.ret_w && uni(A.ret_w[0]) == 0u;
+    DtpQueue dq, dp;
+    if (sparse) {
+        dq.load_live(A.dtp_slots, A.dtp_qn, A.dtp_tiles, A.dtp_cbase + blockIdx.y, q0, q0 < Q1);
+        dp.load_live(A.dtp_pslots, A.dtp_pqn, A.dtp_tiles, A.dtp_cbase + blockIdx.y, q0, q0 < Q1);
+    } else if (store) {
+        dq.load(A, A.dtp_cbase + blockIdx.y, q0, q0 < Q1);
+    }
     const bool dany = __ballot(dq.q0 != ~0u) != 0;
     if (A.req_err && any) {
         uint32_t masks = 0;
@@ -1626,6 +1670,34 @@ extern "C" __global__ __launch_bounds__(256) void mxp_fill_dtp_kernel(mxp_kargs 
     if (!store) return;
     const bool nt = !(A.flags & 128u);
     typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    if (sparse) {
+        // every other row holds the zeros the previous evaluation left.  A row the previous queue
+        // alone names is stored as zeros; one both name, as the current pairs.  Plain stores: a lone
+        // 16-byte row gains nothing from bypassing the cache (MXP_DEBUG_FLAGS 4194304: non-temporal)
+        const bool snt = (A.flags & 4194304u) != 0u;
+        // a lane walks the groups its own two queues name, in ascending order
+        for (;;) {
+            const uint32_t g = min(dq.head_group(), dp.head_group());
+            if (g >= n) break;  // (256: both queues empty)
+            uint32_t m[4] = {0u, 0u, 0u, 0u}, z[4] = {0u, 0u, 0u, 0u};
+            const bool cur = dq.take(g, m);
+            const bool was = dp.take(g, z);
+            if (cur || was) {
+                const uint64_t at = (uint64_t)(g0 + g) * N + q0;
+                if (vec) {
+                    const v4u mv = v4u{m[0], m[1], m[2], m[3]};
+                    if (snt)
+                        __builtin_nontemporal_store(mv, (v4u*)(A.out_match + at));
+                    else
+                        *(v4u*)(A.out_match + at) = mv;
+                } else {
+                    for (uint32_t r = 0; r < 4; r++)
+                        if (q0 + r < Q1) A.out_match[at + r] = m[r];
+                }
+            }
+        }
+        return;
+    }
     for (uint32_t g = 0; g < n; g++) {
         const uint32_t mask = uni(A.fill_masks[moff + g]);
         uint32_t m[4] = {0u, 0u, 0u, 0u}, e[4];
@@ -2011,6 +2083,22 @@ MXP_VTFILL_IMM(8)
 extern "C" __global__ __launch_bounds__(256) void mxp_dtp_sort_kernel(mxp_kargs A) {
     // the next evaluation's overflow counters (kargs.dtp_ovf_next): reset here, no memset launch
     if (blockIdx.x == 0 && threadIdx.x < 2u && A.dtp_ovf_next) A.dtp_ovf_next[threadIdx.x] = 0u;
+    // A retained match bitmap (kargs.ret_w): the bits the previous evaluation's overflow list OR-ed
+    // in after its fill are in no slot row, so they are cleared here, before this evaluation's fill
+    // (afterwards a clear could wipe a bit that is true again).  If that list was full, its index
+    // re-run OR-ed pairs nobody recorded: ret_w[0] tells the fill to store every row.
+    if (A.ret_w) {
+        const bool full = uni(A.dtp_povf_n[1]) != 0u;
+        if (blockIdx.x == 0 && threadIdx.x == 0) {
+            A.ret_w[0] = full ? 1u : 0u;
+            if (full) A.ret_w[1] += 1u;
+        }
+        const uint32_t no = full ? 0u : min(uni(A.dtp_povf_n[0]), A.dtp_ovf_cap);
+        for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i < no; i += gridDim.x * 256u) {
+            const uint32_t q = A.dtp_povf[2ull * i], e = A.dtp_povf[2ull * i + 1];
+            if (!(e >> 31)) atomicAnd(A.out_match + (uint64_t)(e >> 5) * A.n + q, ~(1u << (e & 31u)));
+        }
+    }
     // entries per (chunk of the window, quad): two u16 counters per word (a quad gets at most 4 x 512
     // pairs of one chunk)
     __shared__ uint32_t cnt[MXP_DTP_WIN * 128u];

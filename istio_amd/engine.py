@@ -66,6 +66,7 @@ SIGNATURES = {
     "mxp_batch_pack_host": (ctypes.c_int, [_VP, _VP, ctypes.POINTER(ctypes.c_uint64), ctypes.c_uint32]),
     "mxp_batch_free": (None, [_VP, _VP]),
     "mxp_batch_eval_device": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP]),
+    "mxp_match_retain": (ctypes.c_int, [_VP, _VP, ctypes.c_size_t]),
     "mxp_hits_device": (ctypes.c_int, [_VP, _VP, ctypes.c_uint32, _VP, _VP]),
     "mxp_rule_count": (ctypes.c_uint32, [_VP]),
     "mxp_dbatch_requests": (ctypes.c_uint32, [_VP]),
@@ -493,13 +494,20 @@ class Engine:
         """Request chunks whose guard-index pass overlaps the next chunk's fill (mxp_set_pipeline)."""
         self._check(self.lib.mxp_set_pipeline(self.h, min_requests, max_chunks), "mxp_set_pipeline")
 
+    def match_retain(self, d_match: int = 0, nbytes: int = 0):
+        """mxp_match_retain: from now on only this engine's evaluations write the nbytes at the device
+        pointer d_match, so plain-fill evaluations into it rewrite only the rows that change; no
+        arguments: release.  Every call makes the buffer's contents unknown to the engine."""
+        self._check(self.lib.mxp_match_retain(self.h, _VP(d_match or None), nbytes), "mxp_match_retain")
+
     def set_timing(self, on: bool = True):
         self._check(self.lib.mxp_set_timing(self.h, int(on)), "mxp_set_timing")
 
     def kernel_times(self, n_values: int = 2):
         """[guard/VM kernel ms, guard-index kernel ms] of the last device evaluation (timing on); with
         n_values=3 also [2] = 1.0 when it deferred its index pairs (the index kernel and the pair sort
-        are then in [0], the fills in [1])."""
+        are then in [0], the fills in [1]); with n_values=4 also [3] = 1.0 when it asked for a sparse
+        fill of a retained bitmap (match_retain)."""
         ms = (ctypes.c_float * n_values)()
         n = ctypes.c_uint32()
         self._check(self.lib.mxp_kernel_times(self.h, ms, n_values, ctypes.byref(n)), "mxp_kernel_times")
@@ -827,6 +835,21 @@ class DeviceBatch:
         k = ctypes.c_uint64()
         e._check(e.lib.mxp_debug_dtp_lists(e.h, self.h, out.ctypes.data, out.size, ctypes.byref(k)), "mxp_debug_dtp_lists")
         return dict(zip(("waves", "fills", "vtfills", "cap"), out[:4].tolist())), out[4:k.value].copy()
+
+    def fill_retain_stats(self) -> dict:
+        """Profiling hook (the tail of mxp_debug_dtp_lists), right after a deferred device evaluation
+        of this batch: {"sparse": the launch asked for a sparse fill of a retained bitmap,
+        "fallbacks": sparse fills so far that the device ran densely (previous overflow list full),
+        "live": quad rows with pairs filed by this evaluation, "live_prev": by the previous one into
+        the retained buffer, "full": this evaluation's quads with all 8 slots of a chunk taken,
+        "overflow": the pairs it sent to the overflow list}."""
+        e = self.engine
+        out = np.zeros(10 + (self.n + 63) // 64, dtype=np.uint32)
+        k = ctypes.c_uint64()
+        e._check(e.lib.mxp_debug_dtp_lists(e.h, self.h, out.ctypes.data, out.size, ctypes.byref(k)), "mxp_debug_dtp_lists")
+        if k.value != out.size:
+            raise MxpError("mxp_debug_dtp_lists: no retained-bitmap values")
+        return dict(zip(("sparse", "fallbacks", "live", "live_prev", "full", "overflow"), out[-6:].tolist()))
 
     def eval_compact(self, d_match: int, d_req_err: int, d_hits: int = 0, stream: int = 0):
         """eval_hits() with compact error output: no error bitmap, d_req_err[q] (device u8) = 1 when some
