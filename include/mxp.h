@@ -328,8 +328,9 @@ int mxp_listentry_check(mxp_engine* eng, const mxp_list* list, int blacklist, co
  *
  * mxp_quota_alloc: n requests in arrival order -- key id, QuotaArgs.QuotaAmount (> 0 alloc, < 0
  * free, 0 nothing), QuotaArgs.BestEffort -- all at time now_ns (currentTick = now_ns / 100 ms).
- * granted[i] = QuotaResult.Amount.  State persists across calls.  DeduplicationID handling
- * (dedup.go handleDedup) stays with the caller.  mxp_quota_alloc_device takes device arrays and can
+ * granted[i] = QuotaResult.Amount.  State persists across calls.  These two calls take no
+ * DeduplicationID (dedup.go handleDedup): that is mxp_quota_alloc_dedup, below, on the same key
+ * state.  mxp_quota_alloc_device takes device arrays and can
  * accumulate per-key granted deltas (allocs - frees) into d_delta (i64[n_keys]) for the cross-GPU
  * all-reduce; a device key id >= n_keys is granted 0 and touches no key's state (the
  * host mxp_quota_alloc rejects it with MXP_ERR_ARG).  Multi-GPU: each key has one owner rank and its
@@ -344,6 +345,53 @@ int mxp_quota_alloc(mxp_engine* eng, mxp_quota* quota, uint32_t n, const uint32_
 int mxp_quota_alloc_device(mxp_engine* eng, mxp_quota* quota, uint32_t n, const uint32_t* d_key,
                            const int64_t* d_amount, const uint8_t* d_best_effort, int64_t now_ns, void* stream,
                            int64_t* d_granted, int64_t* d_delta);
+/*
+ * HandleQuota with its DeduplicationID (mixer/adapter/memquota/dedup.go:61-116 handleDedup around
+ * memquota.go:118-211 alloc / free).  Each mxp_quota has one dedup state, as handler.common: two
+ * generations, recent and old, of id bytes -> (amount, exp), shared by allocs and frees and by all
+ * keys; created by the first of these calls (a quota that never sees one allocates nothing for it).
+ * Request i carries the id id_bytes[id_off[i] .. id_off[i + 1]) (compared as bytes; the empty id is
+ * an id like any other).  For the requests of a call taken in arrival order:
+ *   amount 0: granted 0, valid 0, dup 0; neither looked up nor stored (memquota.go:107-116);
+ *   an id held by recent, else old (dedup.go:73-83): the stored amount, dup 1, no key state touched
+ *     and nothing added to d_delta; an alloc's valid_ns = max(0, exp - now_ns), where exp is set only
+ *     by a window alloc that returned a time, a free's valid_ns = 0 (memquota.go:171, 207-210);
+ *   otherwise (dedup.go:85-86) the request with the lowest arrival index among the call's requests
+ *     with that id is replayed with its own key, amount and best-effort flag, exactly as
+ *     mxp_quota_alloc would, and its result is stored in recent: dup 0, valid_ns = the key's
+ *     ValidDuration when the key is a window, the amount > 0 and the request was best effort or
+ *     granted > 0 (memquota.go:146-156; exp = now_ns + ValidDuration), else 0 (no exp).  Every later
+ *     request of the call with that id gets that stored result as a hit at the same now_ns would,
+ *     whatever its own key, sign or amount: dup 1, no key state touched.
+ * valid_ns[i] = QuotaResult.ValidDuration in ns; dup[i] = 1 where the reference logs "Quota
+ * operation satisfied through deduplication" (dedup.go:91-93).  valid_ns and dup may be NULL.
+ * mxp_quota_alloc and mxp_quota_alloc_device may be mixed with these calls on one quota: they share
+ * the key state and neither read nor write the dedup state.
+ *
+ * mxp_quota_alloc_dedup (host arrays): id_off[0] must be 0 and id_off non-decreasing, keys below
+ * n_keys; else MXP_ERR_ARG, the message naming the request.
+ * mxp_quota_alloc_dedup_device (device arrays, enqueued on `stream`, nothing synchronised unless the
+ * dedup table has to grow): trusts its offsets as mxp_quota_alloc_device trusts its keys; a key id
+ * >= n_keys is granted 0 and stored like any replayed request.  d_id_bytes is 8-byte aligned and
+ * has 16 readable bytes of slack past id_bytes_total (ids are hashed and compared a u64 word at a
+ * time).  d_valid_ns, d_dup and d_delta may be NULL.  At most 2^30 requests per call.
+ * mxp_quota_dedup_reap (dedup.go:103-116 reapDedup): old <- recent, recent <- empty; the caller's
+ * ticker of MinDeduplicationDuration calls it (memquota.go:256, 289-291).
+ * mxp_quota_dedup_stats: out = {ids in recent, ids in old, recent's table slots, recent's id pool
+ * bytes}; synchronises the device.
+ * Streams: one quota's calls -- plain, dedup and reap -- run on one stream at a time (the key state
+ * and the dedup state are read and written in stream order); a caller that changes streams orders
+ * them itself.
+ */
+int mxp_quota_alloc_dedup(mxp_engine* eng, mxp_quota* quota, uint32_t n, const uint32_t* key, const int64_t* amount,
+                          const uint8_t* best_effort, const uint8_t* id_bytes, const uint32_t* id_off, int64_t now_ns,
+                          int64_t* granted, int64_t* valid_ns, uint8_t* dup);
+int mxp_quota_alloc_dedup_device(mxp_engine* eng, mxp_quota* quota, uint32_t n, const uint32_t* d_key,
+                                 const int64_t* d_amount, const uint8_t* d_best_effort, const uint8_t* d_id_bytes,
+                                 const uint32_t* d_id_off, uint32_t id_bytes_total, int64_t now_ns, void* stream,
+                                 int64_t* d_granted, int64_t* d_valid_ns, uint8_t* d_dup, int64_t* d_delta);
+int mxp_quota_dedup_reap(mxp_engine* eng, mxp_quota* quota, void* stream);
+int mxp_quota_dedup_stats(mxp_engine* eng, mxp_quota* quota, uint64_t out[4]);
 
 /*
  * Regex compiler check (host only; test and tooling hook): compiles `pattern` with the engine's Go

@@ -3,15 +3,17 @@
 // Reference: mixer/adapter/memquota/memquota.go (HandleQuota, alloc, free), rollingWindow.go,
 // dedup.go (ticksPerSecond = 10, currentTick = now.UnixNano() / nanosPerTick).  The caller resolves
 // each request's quota key (makeKey(instance.Name, instance.Dimensions)) to a dense key id and the
-// key's limit (limit(): the first override whose dimensions match, else the default), and keeps
-// DeduplicationID handling (handleDedup) -- the engine owns the per-key state and the arithmetic.
+// key's limit (limit(): the first override whose dimensions match, else the default) -- the engine
+// owns the per-key state and the arithmetic.  DeduplicationID handling (handleDedup) is
+// quota_dedup.cpp: passes before and after this replay, which sees amount 0 for every request
+// answered from the dedup map.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
 
-#include "engine_impl.h"
 #include "quota_args.h"
+#include "quota_impl.h"
 
 extern "C" hipError_t mxp_quota_sort(void* tmp, size_t* tmp_bytes, const uint32_t* key, uint32_t n_keys,
                                      uint32_t* keys_in, uint32_t* keys_out, uint32_t* idx_in, uint32_t* idx_out,
@@ -20,13 +22,6 @@ extern "C" uint32_t mxp_quota_piece_waves(uint32_t n);
 extern "C" size_t mxp_quota_bucket_words(uint32_t n, uint32_t n_keys);
 extern "C" hipError_t mxp_launch_quota(const mxp_quota_args* a, uint32_t* bucketed,
                                        hipStream_t s);
-
-struct mxp_quota {
-    uint32_t n_keys = 0;
-    DevBuf max_amount, ticks, cells, avail, win_cur, win_tick, slot_off, slots;
-    DevBuf keys_clamped, keys_sorted, idx_in, order, seg_start, tmp, samt, sbe, big, prec, done;
-    size_t cap = 0, tmp_bytes = 0, radix_cap = 0, bucket_cap = 0;  // (tmp: the radix sort's or the bucketing's)
-};
 
 constexpr uint32_t kMaxBins = 4096;  // keys + the sentinel bucketed in LDS (quota.hip mxp_quota_hist)
 
@@ -40,6 +35,7 @@ int mxp_quota_create(mxp_engine* eng, uint32_t n_keys, const int64_t* max_amount
     if ((e = hipSetDevice(eng->device)) != hipSuccess) return eng->hipfail(e, "hipSetDevice");
     std::unique_ptr<mxp_quota> Q(new mxp_quota());
     Q->n_keys = n_keys;
+    Q->valid_ns.assign(valid_duration_ns, valid_duration_ns + n_keys);
     std::vector<uint32_t> ticks(n_keys);
     std::vector<uint64_t> off(n_keys + 1, 0);
     for (uint32_t k = 0; k < n_keys; k++) {

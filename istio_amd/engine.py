@@ -95,6 +95,12 @@ SIGNATURES = {
     "mxp_quota_alloc_device": (ctypes.c_int, [_VP, _VP, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_void_p]),
+    "mxp_quota_alloc_dedup": (ctypes.c_int, [_VP, _VP, ctypes.c_uint32, _VP, _VP, _VP, _VP, _VP, ctypes.c_int64,
+                                             _VP, _VP, _VP]),
+    "mxp_quota_alloc_dedup_device": (ctypes.c_int, [_VP, _VP, ctypes.c_uint32, _VP, _VP, _VP, _VP, _VP,
+                                                    ctypes.c_uint32, ctypes.c_int64, _VP, _VP, _VP, _VP, _VP]),
+    "mxp_quota_dedup_reap": (ctypes.c_int, [_VP, _VP, _VP]),
+    "mxp_quota_dedup_stats": (ctypes.c_int, [_VP, _VP, _VP]),
     "mxp_batch_eval_device_hits": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "mxp_batch_eval_device_compact": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "mxp_set_timing": (ctypes.c_int, [_VP, ctypes.c_int]),
@@ -1107,6 +1113,49 @@ class QuotaHandle:
         self.eng._check(self.eng.lib.mxp_quota_alloc_device(self.eng.h, self.h, n, d_keys, d_amounts, d_be,
                                                             int(now_ns), stream, d_granted, d_delta or None),
                         "mxp_quota_alloc_device")
+
+    def alloc_dedup(self, keys, amounts, best_effort, ids, now_ns: int, id_off=None):
+        """mxp_quota_alloc_dedup: HandleQuota with each request's DeduplicationID (`ids`: a sequence of
+        bytes) -> (granted, valid_ns, dup).  id_off (tests of the host checks): `ids` is then the id
+        blob itself and id_off its n + 1 offsets."""
+        k = np.ascontiguousarray(keys, dtype=np.uint32)
+        a = np.ascontiguousarray(amounts, dtype=np.int64)
+        b = np.ascontiguousarray(best_effort, dtype=np.uint8)
+        if id_off is None:
+            off = np.zeros(len(k) + 1, dtype=np.int64)
+            if len(ids) == len(k):
+                off[1:] = np.cumsum(np.fromiter((len(i) for i in ids), dtype=np.int64, count=len(ids)))
+            if len(ids) != len(k) or off[-1] >= 1 << 32:
+                raise ValueError("one id per request, under 4 GiB in all")
+            blob = b"".join(ids)
+        else:
+            off, blob = id_off, bytes(ids)
+        off = np.ascontiguousarray(off, dtype=np.uint32)
+        blob = np.frombuffer(blob + b"\0", dtype=np.uint8)  # (never empty: .ctypes.data of an empty array is 0)
+        granted = np.zeros(len(k), dtype=np.int64)
+        valid = np.zeros(len(k), dtype=np.int64)
+        dup = np.zeros(len(k), dtype=np.uint8)
+        self.eng._check(self.eng.lib.mxp_quota_alloc_dedup(self.eng.h, self.h, len(k), k.ctypes.data, a.ctypes.data,
+                                                           b.ctypes.data, blob.ctypes.data, off.ctypes.data,
+                                                           int(now_ns), granted.ctypes.data, valid.ctypes.data,
+                                                           dup.ctypes.data), "mxp_quota_alloc_dedup")
+        return granted, valid, dup
+
+    def alloc_dedup_device(self, n, d_keys, d_amounts, d_be, d_id_bytes, d_id_off, id_bytes_total, now_ns, stream,
+                           d_granted, d_valid_ns=None, d_dup=None, d_delta=None):
+        """mxp_quota_alloc_dedup_device: device pointers; the id blob 8-byte aligned with 16 bytes of slack."""
+        self.eng._check(self.eng.lib.mxp_quota_alloc_dedup_device(
+            self.eng.h, self.h, n, d_keys, d_amounts, d_be, d_id_bytes, d_id_off, int(id_bytes_total), int(now_ns),
+            stream, d_granted, d_valid_ns or None, d_dup or None, d_delta or None), "mxp_quota_alloc_dedup_device")
+
+    def reap(self, stream=0):
+        """mxp_quota_dedup_reap (reapDedup): old <- recent, recent <- empty."""
+        self.eng._check(self.eng.lib.mxp_quota_dedup_reap(self.eng.h, self.h, stream or None), "mxp_quota_dedup_reap")
+
+    def dedup_stats(self) -> dict:
+        out = np.zeros(4, dtype=np.uint64)
+        self.eng._check(self.eng.lib.mxp_quota_dedup_stats(self.eng.h, self.h, out.ctypes.data), "mxp_quota_dedup_stats")
+        return dict(zip(("recent_ids", "old_ids", "recent_slots", "recent_pool_bytes"), (int(v) for v in out)))
 
     def __del__(self):
         try:
