@@ -156,8 +156,8 @@ typedef struct mxp_kargs {
     // match-plane pairs (dtp_pslots / dtp_pqn, the other scratch generation) and of its overflow list
     // (dtp_povf, dtp_povf_n).  mxp_dtp_sort_kernel clears the previous overflow pairs' bits and
     // writes ret_w[0] (1: that list was full, its re-run OR-ed pairs nobody recorded -- fill densely;
-    // ret_w[1] counts those fallbacks); mxp_fill_dtp_kernel then stores only the quad rows that held a
-    // match-plane pair then or hold one now (null ret_w: every row, as always).
+    // ret_w[1] counts those fallbacks); mxp_fill_tile_kernel then stores only the quad rows that held a
+    // match-plane pair then or hold one now (null ret_w: mxp_fill_dtp_kernel, every row, as always).
     uint32_t* ret_w;
     const uint16_t* dtp_pslots;
     const uint8_t* dtp_pqn;

@@ -1364,20 +1364,7 @@ struct DtpQueue {
         const v4u sl = *(const v4u*)(A.dtp_slots + qi * 8u);
         decode(dk, sl);
     }
-    // load() from either scratch generation (the retained-bitmap fill), the row only behind a nonzero
-    // count: most quads are empty, and their rows are never read
-    __device__ __forceinline__ void load_live(const uint16_t* slots, const uint8_t* qn, uint32_t tiles, uint32_t chunk,
-                                              uint32_t req0, bool in) {
-        if (!in) return;
-        typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-        const uint64_t qi = (uint64_t)chunk * MXP_DTP_ROW(tiles) + (req0 >> 2);
-        const uint32_t dk = qn[qi];
-        if (!dk) return;
-        const v4u sl = *(const v4u*)(slots + qi * 8u);
-        decode(dk, sl);
-    }
-    // The retained-bitmap fill walks a lane's own queue (no wave-wide group loop: a C2 wave's 64
-    // quads hold a dozen pairs between them, in one or two of the chunk's groups each).
+    // The retained-bitmap fill (FillTileItem) walks a lane's own queue, no wave-wide group loop.
     // The group the head entry names, 256 when the queue is empty:
     __device__ __forceinline__ uint32_t head_group() const { return (q0 & 0xFFFFu) == 0xFFFFu ? 256u : (q0 >> 8) & 0xFFu; }
     // the head entries naming group g OR-ed into m, match plane only; whether a match-plane entry
@@ -1620,84 +1607,16 @@ __device__ __forceinline__ void vtfill_wave(const mxp_kargs& A, const mxp_fill* 
             if (anyerr[r] && q0 + r < Q1) A.req_err[q0 + r] = 1;
 }
 
-// mxp_fill_kernel for deferred index pairs (kargs.dtp_slots): one span of 256 requests per wave (a
-// lane owns one quad, whose sorted pairs it merges into each group's words before storing them)
-extern "C" __global__ __launch_bounds__(256) void mxp_fill_dtp_kernel(mxp_kargs A) {
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t wave = uni(threadIdx.x >> 6);
-    const mxp_fill* F = A.fills + blockIdx.y;
-    const uint32_t col = uni(F->col), okset = uni(F->okset), g0 = uni(F->g0), n = uni(F->n), moff = uni(F->moff);
+// The words of one deferred-pair fill chunk for a lane's quad of requests: per group the error
+// words its guard column's kind gives and the quad's sorted pairs (dq) merged in, streamed out
+__device__ __forceinline__ void fill_dtp_groups(const mxp_kargs& A, uint32_t g0, uint32_t n, uint32_t moff,
+                                                const uint32_t (&bad)[4], DtpQueue& dq, uint32_t q0) {
     const uint64_t N = A.n;
     const uint32_t Q1 = A.q1;
-    const uint32_t qw = A.q0 + (blockIdx.x * 4u + wave) * 256u;
-    if (qw >= Q1) return;
-    const uint32_t q0 = qw + lane * 4u;
     const bool vec = (N & 3u) == 0 && (Q1 & 3u) == 0;
-    uint32_t bad[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const bool in = q0 + r < Q1;
-        const uint32_t k = in ? A.kinds[(uint64_t)col * N + q0 + r] : 0u;
-        bad[r] = (in && !((okset >> k) & 1u)) ? ~0u : 0u;
-    }
-    const bool any = (bad[0] | bad[1] | bad[2] | bad[3]) != 0;
-    // (a pair Resolve's evaluation: only the request error flags and records unless pairs overflowed)
-    const bool store = !A.dtp_lazy || uni(*A.dtp_lazy) != 0u;
-    // (a retained bitmap that still holds the previous evaluation's pairs, kargs.ret_w: only the rows
-    // either evaluation names -- unless mxp_dtp_sort_kernel found the previous overflow list full)
-    const bool sparse = A.ret_w && uni(A.ret_w[0]) == 0u;
-    DtpQueue dq, dp;
-    if (sparse) {
-        dq.load_live(A.dtp_slots, A.dtp_qn, A.dtp_tiles, A.dtp_cbase + blockIdx.y, q0, q0 < Q1);
-        dp.load_live(A.dtp_pslots, A.dtp_pqn, A.dtp_tiles, A.dtp_cbase + blockIdx.y, q0, q0 < Q1);
-    } else if (store) {
-        dq.load(A, A.dtp_cbase + blockIdx.y, q0, q0 < Q1);
-    }
     const bool dany = __ballot(dq.q0 != ~0u) != 0;
-    if (A.req_err && any) {
-        uint32_t masks = 0;
-        for (uint32_t g = 0; g < n; g++) masks |= uni(A.fill_masks[moff + g]);
-        if (masks)
-            for (uint32_t r = 0; r < 4; r++)
-                if (bad[r] && q0 + r < Q1) A.req_err[q0 + r] = 1;
-    }
-    if (A.errlog && any)
-        for (uint32_t g = 0; g < n; g++) {
-            const uint32_t mask = uni(A.fill_masks[moff + g]);
-            for (uint32_t r = 0; r < 4; r++)
-                if (bad[r] && q0 + r < Q1) log_guard_errors(A, mask, (g0 + g) * 32u, q0 + r);
-        }
-    if (!store) return;
     const bool nt = !(A.flags & 128u);
     typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-    if (sparse) {
-        // every other row holds the zeros the previous evaluation left.  A row the previous queue
-        // alone names is stored as zeros; one both name, as the current pairs.  Plain stores: a lone
-        // 16-byte row gains nothing from bypassing the cache (MXP_DEBUG_FLAGS 4194304: non-temporal)
-        const bool snt = (A.flags & 4194304u) != 0u;
-        // a lane walks the groups its own two queues name, in ascending order
-        for (;;) {
-            const uint32_t g = min(dq.head_group(), dp.head_group());
-            if (g >= n) break;  // (256: both queues empty)
-            uint32_t m[4] = {0u, 0u, 0u, 0u}, z[4] = {0u, 0u, 0u, 0u};
-            const bool cur = dq.take(g, m);
-            const bool was = dp.take(g, z);
-            if (cur || was) {
-                const uint64_t at = (uint64_t)(g0 + g) * N + q0;
-                if (vec) {
-                    const v4u mv = v4u{m[0], m[1], m[2], m[3]};
-                    if (snt)
-                        __builtin_nontemporal_store(mv, (v4u*)(A.out_match + at));
-                    else
-                        *(v4u*)(A.out_match + at) = mv;
-                } else {
-                    for (uint32_t r = 0; r < 4; r++)
-                        if (q0 + r < Q1) A.out_match[at + r] = m[r];
-                }
-            }
-        }
-        return;
-    }
     for (uint32_t g = 0; g < n; g++) {
         const uint32_t mask = uni(A.fill_masks[moff + g]);
         uint32_t m[4] = {0u, 0u, 0u, 0u}, e[4];
@@ -1721,6 +1640,237 @@ extern "C" __global__ __launch_bounds__(256) void mxp_fill_dtp_kernel(mxp_kargs 
                 if (A.out_err) A.out_err[at + r] = e[r];
             }
         }
+    }
+}
+
+// mxp_fill_kernel for deferred index pairs (kargs.dtp_slots): one span of 256 requests per wave (a
+// lane owns one quad, whose sorted pairs it merges into each group's words before storing them)
+extern "C" __global__ __launch_bounds__(256) void mxp_fill_dtp_kernel(mxp_kargs A) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t wave = uni(threadIdx.x >> 6);
+    const mxp_fill* F = A.fills + blockIdx.y;
+    const uint32_t col = uni(F->col), okset = uni(F->okset), g0 = uni(F->g0), n = uni(F->n), moff = uni(F->moff);
+    const uint64_t N = A.n;
+    const uint32_t Q1 = A.q1;
+    const uint32_t qw = A.q0 + (blockIdx.x * 4u + wave) * 256u;
+    if (qw >= Q1) return;
+    const uint32_t q0 = qw + lane * 4u;
+    uint32_t bad[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const bool in = q0 + r < Q1;
+        const uint32_t k = in ? A.kinds[(uint64_t)col * N + q0 + r] : 0u;
+        bad[r] = (in && !((okset >> k) & 1u)) ? ~0u : 0u;
+    }
+    const bool any = (bad[0] | bad[1] | bad[2] | bad[3]) != 0;
+    // (a pair Resolve's evaluation: only the request error flags and records unless pairs overflowed)
+    const bool store = !A.dtp_lazy || uni(*A.dtp_lazy) != 0u;
+    DtpQueue dq;
+    if (store) dq.load(A, A.dtp_cbase + blockIdx.y, q0, q0 < Q1);
+    if (A.req_err && any) {
+        uint32_t masks = 0;
+        for (uint32_t g = 0; g < n; g++) masks |= uni(A.fill_masks[moff + g]);
+        if (masks)
+            for (uint32_t r = 0; r < 4; r++)
+                if (bad[r] && q0 + r < Q1) A.req_err[q0 + r] = 1;
+    }
+    if (A.errlog && any)
+        for (uint32_t g = 0; g < n; g++) {
+            const uint32_t mask = uni(A.fill_masks[moff + g]);
+            for (uint32_t r = 0; r < 4; r++)
+                if (bad[r] && q0 + r < Q1) log_guard_errors(A, mask, (g0 + g) * 32u, q0 + r);
+        }
+    if (store) fill_dtp_groups(A, g0, n, moff, bad, dq, q0);
+}
+
+// One live item of the retained-bitmap fill: quad `quad` of the tile (first request qt) in plain
+// fill chunk `chunk`, with dkc / dkp pairs filed by the current / the previous evaluation.  Every
+// other row holds the zeros the previous evaluation left.  A row the previous queue alone names is
+// stored as zeros; one both name, as the current pairs.  Each slot row is read only behind its own
+// nonzero count (a stale row under a zero count means nothing).  load() issues the item's loads
+// and finish() consumes them, so a lane keeps the loads of two items in flight together.
+// Plain stores: a lone 16-byte row gains nothing from bypassing the cache (MXP_DEBUG_FLAGS 4194304:
+// non-temporal)
+struct FillTileItem {
+    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    v4u sc, sp;
+    uint32_t g0, n, dkc = 0u, dkp = 0u, q0;
+    // e: chunk << 16 | quad << 8 | current count << 4 | previous count
+    __device__ __forceinline__ void load(const mxp_kargs& A, uint32_t qt, uint32_t e, bool on) {
+        if (!on) return;
+        const uint32_t chunk = e >> 16, quad = (e >> 8) & 0xFFu;
+        dkc = (e >> 4) & 0xFu;
+        dkp = e & 0xFu;
+        q0 = qt + quad * 4u;
+        const uint64_t qi = (uint64_t)(A.dtp_cbase + chunk) * MXP_DTP_ROW(A.dtp_tiles) + (qt >> 2) + quad;
+        if (dkc) sc = *(const v4u*)(A.dtp_slots + qi * 8u);
+        if (dkp) sp = *(const v4u*)(A.dtp_pslots + qi * 8u);
+        g0 = A.fills[chunk].g0;
+        n = A.fills[chunk].n;
+    }
+    __device__ __forceinline__ void finish(const mxp_kargs& A) {
+        const uint64_t N = A.n;
+        const uint32_t Q1 = A.q1;
+        if (!(dkc | dkp) || q0 >= Q1) return;  // (no pair is filed past the batch: defensive)
+        const bool vec = (N & 3u) == 0 && (Q1 & 3u) == 0;
+        const bool snt = (A.flags & 4194304u) != 0u;
+        DtpQueue dq, dp;
+        dq.decode(dkc, sc);
+        dp.decode(dkp, sp);
+        // the groups the two queues name, in ascending order
+        for (;;) {
+            const uint32_t g = min(dq.head_group(), dp.head_group());
+            if (g >= n) break;  // (256: both queues empty)
+            uint32_t m[4] = {0u, 0u, 0u, 0u}, z[4] = {0u, 0u, 0u, 0u};
+            const bool cur = dq.take(g, m);
+            const bool was = dp.take(g, z);
+            if (cur || was) {
+                const uint64_t at = (uint64_t)(g0 + g) * N + q0;
+                if (vec) {
+                    const v4u mv = v4u{m[0], m[1], m[2], m[3]};
+                    if (snt)
+                        __builtin_nontemporal_store(mv, (v4u*)(A.out_match + at));
+                    else
+                        *(v4u*)(A.out_match + at) = mv;
+                } else {
+                    for (uint32_t r = 0; r < 4; r++)
+                        if (q0 + r < Q1) A.out_match[at + r] = m[r];
+                }
+            }
+        }
+    }
+};
+
+// The plain fill of an evaluation into a retained match bitmap that still holds the previous
+// evaluation's pairs (kargs.ret_w, DESIGN.md §4 "Retained match bitmap"): one workgroup per sort tile
+// of 1024 requests covers every plain fill chunk of the tile.
+//  - Kind check, once per tile: thread tid owns quad tid and walks the chunk descriptors (64 of them
+//    a vector load, read back with v_readlane); the quad's kind bytes are loaded once per distinct
+//    guard column (not once per chunk), the request error flags and records are the ones
+//    mxp_fill_dtp_kernel writes.
+//  - ret_w[0] != 0 (mxp_dtp_sort_kernel found the previous overflow list full): every row of every
+//    chunk is stored, through the dense fill's group loop.
+//  - Else the count scan: a tile's 256 count bytes of one (chunk, generation) are one aligned u32
+//    per lane of a wave; wave w takes chunks w, w + 4, ..., MXP_FTQ of them a round with all their
+//    count loads of both generations in flight together (the first round's before the kind check).
+//    A (chunk, quad) whose count is nonzero in either generation is a live item (C2: one in ten);
+//    a round's items are compacted into an LDS queue and run 256 at a time on dense lanes.
+#define MXP_FTQ 8u
+extern "C" __global__ __launch_bounds__(256) void mxp_fill_tile_kernel(mxp_kargs A, uint32_t n_fills) {
+    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uni(tid >> 6);
+    const uint64_t N = A.n;
+    const uint32_t Q1 = A.q1;
+    const uint32_t qt = A.q0 + blockIdx.x * 1024u;  // (a multiple of 1024: mxp_launch_fill)
+    if (qt >= Q1) return;
+    const uint32_t q0 = qt + tid * 4u;
+    const bool dense = uni(A.ret_w[0]) != 0u;
+    const uint64_t row = MXP_DTP_ROW(A.dtp_tiles);
+    uint32_t cw[MXP_FTQ], pw[MXP_FTQ];
+    auto load_counts = [&](uint32_t c0) {
+#pragma unroll
+        for (uint32_t b = 0; b < MXP_FTQ; b++) {  // (clamped chunk: no branch between the loads)
+            const uint32_t c = min(c0 + wave + 4u * b, n_fills - 1u);
+            const uint64_t at = (uint64_t)(A.dtp_cbase + c) * row + (qt >> 2) + lane * 4u;
+            cw[b] = *(const uint32_t*)(A.dtp_qn + at);
+            pw[b] = *(const uint32_t*)(A.dtp_pqn + at);
+        }
+    };
+    if (!dense) load_counts(0u);
+    {
+        const bool kvec = (N & 3u) == 0 && ((uintptr_t)A.kinds & 3u) == 0;
+        uint32_t col = ~0u, okset = 0u, kb = 0u, bad[4] = {0u, 0u, 0u, 0u}, flagged = 0u;
+        bool any = false;
+        for (uint32_t f0 = 0; f0 < n_fills; f0 += 64u) {
+            const uint32_t fl = min(f0 + lane, n_fills - 1u);
+            const uint32_t colv = A.fills[fl].col, okv = A.fills[fl].okset;
+            const uint32_t f1 = min(64u, n_fills - f0);
+            for (uint32_t i = 0; i < f1; i++) {
+                const uint32_t c = __builtin_amdgcn_readlane(colv, i), ok = __builtin_amdgcn_readlane(okv, i);
+                if (c != col) {  // the quad's four kind bytes
+                    kb = 0u;
+                    if (kvec) {
+                        if (q0 < Q1) kb = *(const uint32_t*)(A.kinds + (uint64_t)c * N + q0);
+                    } else {
+                        for (uint32_t r = 0; r < 4; r++)
+                            if (q0 + r < Q1) kb |= (uint32_t)A.kinds[(uint64_t)c * N + q0 + r] << (8u * r);
+                    }
+                }
+                if (c != col || ok != okset) {
+#pragma unroll
+                    for (uint32_t r = 0; r < 4; r++)
+                        bad[r] = (q0 + r < Q1 && !((ok >> ((kb >> (8u * r)) & 0xFFu)) & 1u)) ? ~0u : 0u;
+                    any = (bad[0] | bad[1] | bad[2] | bad[3]) != 0;
+                }
+                col = c;
+                okset = ok;
+                if (!dense && !__ballot(any)) continue;  // (the chunk's groups: only where they are used)
+                const mxp_fill* F = A.fills + f0 + i;
+                const uint32_t g0 = uni(F->g0), n = uni(F->n), moff = uni(F->moff);
+                if (A.req_err && any) {
+                    uint32_t masks = 0;
+                    for (uint32_t g = 0; g < n; g++) masks |= uni(A.fill_masks[moff + g]);
+                    if (masks)
+                        for (uint32_t r = 0; r < 4; r++) flagged |= bad[r] & (1u << r);
+                }
+                // (error records, as the dense fill writes them.  No evaluation reaches this branch
+                // today: only a caller's buffer can be retained, and every entry point that evaluates
+                // into a caller's buffer -- mxp_eval_device*, the group -- runs without records; the
+                // evaluations that log write the engine's own bitmaps.  Kept so that kargs mean the
+                // same in both fills.)
+                if (A.errlog && any)
+                    for (uint32_t g = 0; g < n; g++) {
+                        const uint32_t mask = uni(A.fill_masks[moff + g]);
+                        for (uint32_t r = 0; r < 4; r++)
+                            if (bad[r] && q0 + r < Q1) log_guard_errors(A, mask, (g0 + g) * 32u, q0 + r);
+                    }
+                if (dense) {
+                    DtpQueue dq;
+                    dq.load(A, A.dtp_cbase + f0 + i, q0, q0 < Q1);
+                    fill_dtp_groups(A, g0, n, moff, bad, dq, q0);
+                }
+            }
+        }
+        for (uint32_t r = 0; r < 4; r++)
+            if ((flagged >> r) & 1u) A.req_err[q0 + r] = 1;  // (bad[r]: q0 + r < Q1)
+    }
+    if (dense) return;
+    // the round's live items, compacted (a round holds at most 4 x MXP_FTQ x 256)
+    // (each wave queues its own chunks' items, chunk by chunk: the items a wavefront then runs
+    // together store into the rows of two or three chunks, not of every chunk of the tile)
+    __shared__ uint32_t Q[4u][MXP_FTQ * 256u];
+    __shared__ uint32_t Qn[4u];
+    for (uint32_t c0 = 0; c0 < n_fills; c0 += 4u * MXP_FTQ) {
+        if (c0) load_counts(c0);
+        uint32_t run = 0u;
+#pragma unroll
+        for (uint32_t b = 0; b < MXP_FTQ; b++) {
+            const bool in = c0 + wave + 4u * b < n_fills;
+#pragma unroll
+            for (uint32_t k = 0; k < 4u; k++) {
+                const uint32_t dkc = in ? (cw[b] >> (8u * k)) & 0xFFu : 0u, dkp = in ? (pw[b] >> (8u * k)) & 0xFFu : 0u;
+                const bool on = (dkc | dkp) != 0u;
+                const unsigned long long mask = __ballot(on);
+                const uint32_t before =
+                    __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+                if (on) Q[wave][run + before] = (c0 + wave + 4u * b) << 16 | (lane * 4u + k) << 8 | dkc << 4 | dkp;
+                run += (uint32_t)__builtin_popcountll(mask);
+            }
+        }
+        if (lane == 0u) Qn[wave] = run;
+        __syncthreads();
+        const uint32_t t1 = Qn[0], t2 = t1 + Qn[1], t3 = t2 + Qn[2], total = t3 + Qn[3];
+        auto item = [&](uint32_t i) {  // the i-th item of the four waves' lists
+            const uint32_t w = (i >= t1) + (i >= t2) + (i >= t3);
+            return Q[w][i - (w == 0u ? 0u : w == 1u ? t1 : w == 2u ? t2 : t3)];
+        };
+        for (uint32_t i = tid; i < total; i += 512u) {
+            FillTileItem a, b;
+            a.load(A, qt, item(i), true);
+            b.load(A, qt, item(min(i + 256u, total - 1u)), i + 256u < total);
+            a.finish(A);
+            b.finish(A);
+        }
+        __syncthreads();
     }
 }
 
@@ -3136,6 +3286,11 @@ extern "C" hipError_t mxp_launch_dtp_hits(const uint32_t* part, uint32_t tiles, 
 }
 
 extern "C" hipError_t mxp_launch_fill(const mxp_kargs* args, uint32_t n_fills, hipStream_t s) {
+    if (args->dtp_slots && args->ret_w) {  // a retained bitmap's sparse fill: one workgroup per sort tile
+        if ((args->q0 & 1023u) || n_fills > 65536u) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(mxp_fill_tile_kernel, dim3((args->q1 - args->q0 + 1023u) / 1024u), dim3(256), 0, s, *args, n_fills);
+        return hipGetLastError();
+    }
     if (args->dtp_slots) {
         hipLaunchKernelGGL(mxp_fill_dtp_kernel, dim3((args->q1 - args->q0 + 1023u) / 1024u, n_fills), dim3(256), 0, s, *args);
         return hipGetLastError();
