@@ -365,7 +365,7 @@ int mxp_engine::compile(const char* const* exprs, uint32_t n, int32_t* status) {
         // with /p/): direct postings on the full keys, exact-length ones where the subject must end
         // (MXP_DEBUG_FLAGS 67108864: keep the DFA template -- A/B)
         std::vector<mxp::LiteralKey> keys;
-        if (!(debug_flags & 67108864u) && n < (1u << 23) && mxp::dfa_literal_keys(d, st, 8, 8, &keys)) {
+        if (!(debug_flags & MXP_DBG_KEEP_RX_DFA) && n < (1u << 23) && mxp::dfa_literal_keys(d, st, 8, 8, &keys)) {
             auto& rk = rx_keys_h[rp.rule];
             for (const auto& k : keys) rk.push_back({intern_string(rp.prefix + k.bytes), k.tail ? 2u : k.exact ? 1u : 0u});
             guards[rp.rule].mode = GM_ONLY | GT_PREFIX;
@@ -535,8 +535,8 @@ int mxp_engine::build_plan(Plan& P) {
         // GM_ONLY prefix atoms (`attr.startsWith(K)` alone): a posting IS a true pair.  Equality
         // atoms alone stay with phase 1's group compares -- indexing them too (MXP_DEBUG_FLAGS 512)
         // measured slower on C4 (header equality: 0.35 ms compared, 0.92 ms indexed)
-        bool ok = !(debug_flags & 8u) && !neg &&
-                  ((mode == GM_AND && rule_tmpl[i] != MXP_VM_DONE) || (mode == GM_ONLY && (debug_flags & 512u)) ||
+        bool ok = !(debug_flags & MXP_DBG_NO_INDEX) && !neg &&
+                  ((mode == GM_AND && rule_tmpl[i] != MXP_VM_DONE) || (mode == GM_ONLY && (debug_flags & MXP_DBG_INDEX_EQ_ONLY)) ||
                    (prefix && mode == GM_ONLY));
         if (!ok) {
             if (prefix) {
@@ -548,7 +548,7 @@ int mxp_engine::build_plan(Plan& P) {
         if (mode == GM_ONLY) rule_tmpl[i] = MXP_TMPL_DIRECT;
         indexed[i] = 1;
         P.n_indexed++;
-        if (!(debug_flags & 64u)) {
+        if (!(debug_flags & MXP_DBG_NO_DUP_FOLD)) {
             std::string key((const char*)&gd, sizeof gd);
             key.append((const char*)(all.data() + off[i]), (size_t)(off[i + 1] - off[i]) * sizeof(mxp_vm_ins));
             auto ins = canon_of.emplace(std::move(key), i);
@@ -561,7 +561,7 @@ int mxp_engine::build_plan(Plan& P) {
         const uint64_t k1 = (uint64_t)gd.klo | ((uint64_t)gd.khi << 32);
         mxp::SecondAtom sa;
         std::vector<mxp_vm_ins> code(all.begin() + off[i], all.begin() + off[i + 1]);
-        if (!prefix && mode == GM_AND && !(debug_flags & 16u) && mxp::extract_second_prefix(code, gd.mode >> 16, &sa)) {
+        if (!prefix && mode == GM_AND && !(debug_flags & MXP_DBG_NO_COMPOSITE) && mxp::extract_second_prefix(code, gd.mode >> 16, &sa)) {
             if (sa.direct) {
                 rule_tmpl2[i] = MXP_TMPL_DIRECT;
             } else {
@@ -743,7 +743,7 @@ int mxp_engine::build_plan(Plan& P) {
                     use(rule_tmpl2[r]);
                 }
             }
-        P.tmpl_lite = !(debug_flags & 8388608u);
+        P.tmpl_lite = !(debug_flags & MXP_DBG_NO_TMPL_LITE);
         for (uint32_t i = 0; i < tmpls.size() && P.tmpl_lite; i++) {
             if (!used[i]) continue;
             const mxp_tmpl& t = tmpls[i];
@@ -887,7 +887,7 @@ int mxp_engine::build_plan(Plan& P) {
         const bool only_vt = G.all == 0 && has_vt;
         const bool uniform = !G.vm && (only_vt || (G.all && G.indexed == G.all && G.guarded == G.all && G.nseg == 1 &&
                                                    G.s_cmp == 0 && G.s_rules == G.all)) &&
-                             !deep[g] && !(debug_flags & 32u);
+                             !deep[g] && !(debug_flags & MXP_DBG_NO_UNIFORM);
         if (uniform) {
             mxp_fill* F = fills.empty() ? nullptr : &fills.back();
             const bool joins = F && F->g0 + F->n == g && F->n < fill_chunk &&
@@ -953,7 +953,7 @@ int mxp_engine::build_plan(Plan& P) {
         std::stable_sort(cand.begin(), cand.end(),
                          [&](uint32_t a, uint32_t b) { return aliases_of[a].size() > aliases_of[b].size(); });
         if (cand.size() > 64) cand.resize(64);
-        if (debug_flags & 256u) cand.clear();  // ablation: fan out with atomics
+        if (debug_flags & MXP_DBG_NO_DENSE) cand.clear();  // ablation: fan out with atomics
         dense_of.assign(n, 0xFF);
         std::map<uint32_t, std::vector<uint32_t>> by_word;
         for (uint32_t d = 0; d < cand.size(); d++) {
@@ -1331,7 +1331,7 @@ int mxp_engine::pack_host(const mxp_bag_batch* b, mxp_dbatch* db, PackedHost& H)
     // -- distinct string ids by a bitmap over the id space, plus one class per other kind
     db->vt_mask = 0;
     db->vt_capc.assign(vt_cand_col.size(), 0);
-    if (!(debug_flags & 131072u) && n) {
+    if (!(debug_flags & MXP_DBG_NO_VT) && n) {
         const uint64_t S = G + db->overlay.size();
         uint32_t active = 0;
         std::vector<uint64_t> bits;
@@ -1355,7 +1355,7 @@ int mxp_engine::pack_host(const mxp_bag_batch* b, mxp_dbatch* db, PackedHost& H)
             });
             uint64_t D = (uint64_t)__builtin_popcount(kmask);
             for (uint64_t w : bits) D += (uint64_t)__builtin_popcountll(w);
-            const bool force = (debug_flags & 262144u) != 0;  // tests: value classes at any batch size
+            const bool force = (debug_flags & MXP_DBG_FORCE_VT) != 0;  // tests: value classes at any batch size
             if (D > kVtMaxClasses || (!force && D * 16 > n)) continue;
             uint32_t cap = 64;
             while (cap < 2 * D) cap <<= 1;
@@ -1563,7 +1563,7 @@ void mxp_engine::fill_args(mxp_kargs* A, const mxp_dbatch* db, const Plan& P) co
     A->gk = P.d_gk.as<uint64_t>();
     A->idx = P.d_idx.as<mxp_index>();
     A->hents = P.d_hents.as<mxp_hent>();
-    A->hbits = (debug_flags & 4u) || !P.d_hbits.p ? nullptr : P.d_hbits.as<uint32_t>();
+    A->hbits = (debug_flags & MXP_DBG_NO_HBITS) || !P.d_hbits.p ? nullptr : P.d_hbits.as<uint32_t>();
     A->postings = P.d_postings.as<uint32_t>();
     A->post_tmpl = P.post_tmpl ? 1u : 0u;
     A->tmpl_lite = P.tmpl_lite ? 1u : 0u;
@@ -1681,7 +1681,7 @@ int mxp_engine::pack_dict(mxp_dbatch* db) {
     fill_args(&A, db, *P);
     A.q0 = 0;
     A.q1 = db->n;
-    if (db->vtd_ready && !(debug_flags & 134217728u)) {
+    if (db->vtd_ready && !(debug_flags & MXP_DBG_VT_CLASSIFY)) {
         // the device packer's two-level dictionary (pack.hip mxp_pack_vtd_*): its provisional tables
         // into the final ones (MXP_DEBUG_FLAGS 134217728: the one-level classify kernel -- A/B)
         mxp_vtd_final_args F;
@@ -1785,7 +1785,7 @@ int mxp_engine::launch_body(mxp_dbatch* db, hipStream_t s, uint32_t* d_match, ui
     if (to_ret) ret.valid = false;
     // guards on: guard-only groups through the lean kernel, the rest through the VM kernel;
     // guards off (Eval, ablation): every group through the VM kernel
-    const bool guards_on = !d_vals && !(debug_flags & 2u);
+    const bool guards_on = !d_vals && !(debug_flags & MXP_DBG_NO_GUARDS);
     // value classes only for plain predicate evaluations: Eval mode, referenced attributes and
     // recomputed error windows (which need every record) run plan 0
     const uint32_t mask = (guards_on && !refs_on && !win_log_cap) ? db->vt_mask : 0u;
@@ -1848,7 +1848,7 @@ int mxp_engine::launch_body(mxp_dbatch* db, hipStream_t s, uint32_t* d_match, ui
     }
     if (A.n == 0 || A.n_rules == 0) return MXP_OK;
     // guard-index phase: predicate mode only (Eval runs whole programs in mxp_eval_kernel)
-    const bool use_index = !d_vals && !(debug_flags & 2u) && P->n_idx > 0;
+    const bool use_index = !d_vals && !(debug_flags & MXP_DBG_NO_GUARDS) && P->n_idx > 0;
     if (!use_index) A.n_idx = 0;
     auto gy_of = [&](uint32_t ng) { return (ng + 4 * A.groups_per_wave - 1) / (4 * A.groups_per_wave); };
     if (timing && (e = hipEventRecord(ev[0], s)) != hipSuccess) return hipfail(e, "event");
@@ -1906,7 +1906,7 @@ int mxp_engine::launch_body(mxp_dbatch* db, hipStream_t s, uint32_t* d_match, ui
     // histograms, summed by mxp_dtp_hits_kernel): the hit counters are fused into every kernel of
     // the evaluation, whatever the device gate says, and the bitmap is not streamed again
     // (eval_device_hits; MXP_DEBUG_FLAGS 1048576 keeps the streaming counters)
-    const bool dtp_count = dtp_on && A.hits && !(debug_flags & 1048576u) && A.n_rules <= kDtpHist;
+    const bool dtp_count = dtp_on && A.hits && !(debug_flags & MXP_DBG_HITS_STREAM) && A.n_rules <= kDtpHist;
     last_dtp_counted = dtp_count;
     // (and the true-pair count that steers the fused / streamed choice is not kept: one atomic per
     // index wave on one address congests its L2 channel -- C2 0.517 -> 0.409 ms same-box, profiles/r3_v6_ab_nostats_c2.log)
@@ -2712,7 +2712,7 @@ static int eval_device_hits(mxp_engine* eng, mxp_dbatch* db, void* stream, uint3
     // evaluation sets the next one's gate from its true pairs per request): no host round trip and no
     // stale decision when evaluations are queued back to back.
     const uint32_t R = (uint32_t)eng->rules.size(), W = (R + 31) / 32;
-    const uint32_t force = (eng->debug_flags & 524288u) ? 1u : (eng->debug_flags & 1048576u) ? 2u : 0u;
+    const uint32_t force = (eng->debug_flags & MXP_DBG_HITS_FUSED) ? 1u : (eng->debug_flags & MXP_DBG_HITS_STREAM) ? 2u : 0u;
     // (ordered after the previous evaluation's gate update even when the caller switched streams)
     if (eng->stats_pending && eng->stats_stream != s && (e = hipStreamWaitEvent(s, eng->stats_ev, 0)) != hipSuccess)
         return eng->hipfail(e, "stats wait");
@@ -3177,12 +3177,9 @@ int mxp_engine::expand_class_errors(const mxp_bag_batch* batch, mxp_dbatch* db, 
         const uint32_t s = vt_slot_of_rule[r.rule];
         const uint32_t a = (uint32_t)__builtin_popcount(last_mask & ((1u << s) - 1u));
         const uint32_t k = cls[(size_t)a * pitch + r.req];
-        // (every request of the class prints the same value: one text per class record)
-        int32_t text = -1;
-        if (r.code >= ERR_CONV_S && r.code <= ERR_CONV_D) {
-            text = (int32_t)last_rec_texts.size();
-            last_rec_texts.push_back(format_error(batch, db, r));
-        }
+        // (a conversion error prints the request's own value, and a class of a kind other than
+        // string holds every value of that kind, mxp_vt_key: one text per request)
+        const bool conv = r.code >= ERR_CONV_S && r.code <= ERR_CONV_D;
         for (uint32_t i = start[a][k]; i < start[a][k + 1]; i++) {
             if (emitted >= room) {
                 errors_complete = false;
@@ -3190,6 +3187,11 @@ int mxp_engine::expand_class_errors(const mxp_bag_batch* batch, mxp_dbatch* db, 
             }
             mxp_err_rec x = r;
             x.req = reqs[a][i];
+            int32_t text = -1;
+            if (conv) {
+                text = (int32_t)last_rec_texts.size();
+                last_rec_texts.push_back(format_error(batch, db, x));
+            }
             last_recs.push_back(x);
             if (text >= 0 || !last_rec_text.empty()) {  // (the index exists once a record has a text)
                 last_rec_text.resize(last_recs.size() - 1, -1);

@@ -552,17 +552,11 @@ struct mxp_engine : public mxp::LowerTables {
     static constexpr uint32_t kDtpChunksMax = 16;
     uint32_t dtp_chunks = 1;
     hipEvent_t dtp_cev[kDtpChunksMax + 1] = {};
-    // MXP_DEBUG_FLAGS, ablation only: 1 no in-wave VM, 2 no guards (results invalid), 8 no guard index,
-    // 16 no composite index, 64 no duplicate folding, 128 plain fill stores, 256 no dense injection,
-    // 512 index equality-only guards too, 524288 / 1048576 fused / streaming hit counters forced,
-    // 2097152 value-class fill chunks gather from global memory (no LDS staging), 16384 long posting
-    // lists of the guard index walked by their own lane (no wave-cooperative expansion; same results),
-    // 4194304 non-temporal row stores in the retained-bitmap fill
     // fill layout (same-box A/B on C2, profiles/r1_v17_ab_fill*.log: span 1 / chunk 32 0.945 ms,
     // span 4 0.832-0.836, span 4 / chunk 16 0.831; spans 3, 5, 6, 8 and chunks 4..1000 no better)
     uint32_t fill_chunk = MXP_FILL_CHUNK;  // MXP_FILL_CHUNK: groups per fill chunk
     uint32_t fill_span = 4;                // MXP_FILL_SPAN: 256-request spans per fill wave (1..8)
-    uint32_t debug_flags = 0;
+    uint32_t debug_flags = 0;              // MXP_DEBUG_FLAGS: the MXP_DBG_* bits (kargs.h)
     // guard-index hash tables hold >= 2^(1 + index_sparsity) slots per key (MXP_INDEX_SPARSITY):
     // a lower load factor shortens the probe chains of the many misses (prefix probes at every key
     // length).  Same-box A/B (profiles/r2_v7_ab_sparse_*.log), ms per evaluation for 0 / 1 / 2 / 3:

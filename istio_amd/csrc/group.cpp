@@ -489,7 +489,8 @@ int mxp_group_create(const int* devices, uint32_t n, uint32_t flags, mxp_group**
     for (uint32_t a = 0; a < n; a++)
         for (uint32_t b = a + 1; b < n; b++) distinct &= devices[a] != devices[b];
     const bool want_rccl = (n > 1 || (flags & MXP_GROUP_RCCL_SINGLE)) && !(flags & MXP_GROUP_HOST_REDUCE);
-    g->reduce = n > 1 || (flags & (MXP_GROUP_RCCL_SINGLE | MXP_GROUP_HOST_REDUCE)) ? MXP_REDUCE_HOST : MXP_REDUCE_NONE;
+    const uint32_t reduce_flags = MXP_GROUP_RCCL_SINGLE | MXP_GROUP_HOST_REDUCE;
+    g->reduce = n > 1 || (flags & reduce_flags) ? MXP_REDUCE_HOST : MXP_REDUCE_NONE;
     if (want_rccl && !distinct) {
         g->last_error = "reduction on the host: a device appears twice in the group (RCCL needs one rank per GPU)";
     } else if (want_rccl) {

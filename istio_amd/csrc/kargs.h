@@ -20,6 +20,37 @@
 // plus 64 -- rows exactly 2^k requests apart would alias HBM channels across the fill's slots
 #define MXP_VT_PITCH(n) ((((uint64_t)(n) + 3u) & ~(uint64_t)3u) + 64u)
 
+// MXP_DEBUG_FLAGS (mxp_engine::debug_flags, copied to kargs.flags): ablation, A/B and test switches.
+// The environment variable, the tests, tools/ and DESIGN.md give them by number: values never change.
+enum : uint32_t {
+    MXP_DBG_NO_WAVE_VM = 1u << 0,        // the VM kernels skip the in-wave continuation pass (results invalid)
+    MXP_DBG_NO_GUARDS = 1u << 1,         // no guards and no guard index: whole programs in the VM kernel
+    MXP_DBG_NO_HBITS = 1u << 2,          // index probes load the entry pair first (no occupancy bitmaps)
+    MXP_DBG_NO_INDEX = 1u << 3,          // no rule goes to the guard index
+    MXP_DBG_NO_COMPOSITE = 1u << 4,      // no composite (second-atom prefix) index
+    MXP_DBG_NO_UNIFORM = 1u << 5,        // no group counts as uniform: no fill chunks
+    MXP_DBG_NO_DUP_FOLD = 1u << 6,       // duplicate indexed rules are not folded into aliases
+    MXP_DBG_PLAIN_STORES = 1u << 7,      // the streaming fills store plainly, not non-temporally
+    MXP_DBG_NO_DENSE = 1u << 8,          // no dense injection: aliases fan out with atomics
+    MXP_DBG_INDEX_EQ_ONLY = 1u << 9,     // equality-only guards go to the index too
+    MXP_DBG_PROBES_ONLY = 1u << 10,      // the index kernel probes but processes no pair (results invalid)
+    MXP_DBG_INDEX5 = 1u << 13,           // mxp_index5_kernel: the index body at 5 waves/SIMD
+    MXP_DBG_NO_COOP_LISTS = 1u << 14,    // long posting lists walked by their own lane (same results)
+    MXP_DBG_GUARD1 = 1u << 16,           // mxp_guard_kernel in place of mxp_guard2_kernel
+    MXP_DBG_NO_VT = 1u << 17,            // no value classes
+    MXP_DBG_FORCE_VT = 1u << 18,         // value classes at any batch size (tests)
+    MXP_DBG_HITS_FUSED = 1u << 19,       // fused hit counters forced
+    MXP_DBG_HITS_STREAM = 1u << 20,      // streaming hit counters forced (also: deferred pairs not counted in the sort)
+    MXP_DBG_VTFILL_GLOBAL = 1u << 21,    // mxp_vtfill_kernel: class words gathered from global memory, no LDS staging
+    MXP_DBG_TILE_NT_STORES = 1u << 22,   // non-temporal row stores in the retained-bitmap fill
+    MXP_DBG_NO_TMPL_LITE = 1u << 23,     // the full index kernel where the lite one would do
+    MXP_DBG_VTFILL_LDS = 1u << 25,       // mxp_vtfill_lds_kernel where the immediate-offset fill would run
+    MXP_DBG_KEEP_RX_DFA = 1u << 26,      // literal-alternation regexps keep their DFA template (no literal keys)
+    MXP_DBG_VT_CLASSIFY = 1u << 27,      // the one-level classify kernel, not the device packer's dictionary
+    MXP_DBG_RESOLVE_BITMAP = 1u << 28,   // Resolve through the error bitmap, not the compact outputs
+    MXP_DBG_FINISH_FAIL = 1u << 29,      // the next finish_pack fails once, after the class tables (tests)
+};
+
 typedef struct mxp_kargs {
     // rule set (uploaded once per config snapshot)
     const mxp_vm_ins* prog;      // all rules' programs, concatenated
@@ -95,7 +126,7 @@ typedef struct mxp_kargs {
     uint32_t* refcount;
     uint32_t refcap;
     uint32_t errcap;
-    uint32_t flags;              // debug / ablation: 1 = skip in-wave VM, 2 = no guards (results invalid)
+    uint32_t flags;              // debug / ablation: the MXP_DBG_* bits above
     const uint32_t* fill_masks;  // mxp_fill_kernel: rules of each group of a chunk (mxp_fill.moff)
     // value classes (kernels.hip mxp_vt_*; null gvt_off: none)
     const uint32_t* gvt_off;     // [n_words + 1] merge entries of each group

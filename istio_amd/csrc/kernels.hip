@@ -719,7 +719,7 @@ __device__ __forceinline__ void eval_groups(const mxp_kargs& A, uint64_t (*regs)
     const uint32_t i0 = (blockIdx.y * 4u + wave) * A.groups_per_wave;
     const uint32_t i1 = min(i0 + A.groups_per_wave, A.n_glist);
     // Eval mode (out_vals) needs every result register: whole programs, no guards, no index
-    const bool guards_on = !(A.out_vals || (A.flags & 2u));
+    const bool guards_on = !(A.out_vals || (A.flags & MXP_DBG_NO_GUARDS));
     uint32_t cached = MXP_VM_DONE;
     uint32_t ck = MXP_ABSENT;
     uint64_t cv = 0;
@@ -795,7 +795,7 @@ __device__ __forceinline__ void eval_groups(const mxp_kargs& A, uint64_t (*regs)
             }
             // ---- phase 2 (in-wave)
             if (kVM) {
-                for (uint32_t bits = wave_or(cont); bits && !(A.flags & 1u); bits &= bits - 1) {
+                for (uint32_t bits = wave_or(cont); bits && !(A.flags & MXP_DBG_NO_WAVE_VM); bits &= bits - 1) {
                     const uint32_t k = __builtin_ctz(bits);
                     const uint32_t bit = 1u << k;
                     const bool need = (cont & bit) != 0;
@@ -999,6 +999,94 @@ extern "C" __global__ __launch_bounds__(256) void mxp_eval_deep_refs_kernel(mxp_
     eval_groups<true, true>(A, regs);
 }
 
+// ---- Pieces every writer of the fill path shares (mxp_fill_kernel, mxp_fill_dtp_kernel,
+// mxp_fill_tile_kernel, vtfill_wave, vtfill_imm_body).  A lane owns a quad: requests q0 .. q0 + 3.
+typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+// a fill chunk's descriptor (wave-uniform)
+struct FillChunk {
+    uint32_t col, okset, g0, n, moff;
+    __device__ __forceinline__ explicit FillChunk(const mxp_fill* F)
+        : col(uni(F->col)), okset(uni(F->okset)), g0(uni(F->g0)), n(uni(F->n)), moff(uni(F->moff)) {}
+};
+// Rows are 16-byte aligned and every quad is whole: a quad below q1 then moves as one vector
+// (4 kind bytes, 4 x u16 classes, 4 words of a bitmap row).  Wave-uniform.
+__device__ __forceinline__ bool quads_vec(const mxp_kargs& A) { return ((A.n | A.q0 | A.q1) & 3u) == 0; }
+// the quad's four kind bytes of column col, packed (byte r: request q0 + r, zero past q1)
+__device__ __forceinline__ uint32_t quad_kinds(const mxp_kargs& A, uint32_t col, uint32_t q0, bool vec) {
+    const uint8_t* K = A.kinds + (uint64_t)col * A.n + q0;
+    if (vec && q0 < A.q1) return *(const uint32_t*)K;
+    uint32_t k4 = 0u;
+#pragma unroll
+    for (uint32_t r = 0; r < 4; r++)
+        if (q0 + r < A.q1) k4 |= (uint32_t)K[r] << (8u * r);
+    return k4;
+}
+// ~0 when a request (in: below q1) of kind k fails the type check of a guard that accepts the kinds of okset
+__device__ __forceinline__ uint32_t kind_bad(uint32_t okset, uint32_t k, bool in) {
+    return (in && !((okset >> k) & 1u)) ? ~0u : 0u;
+}
+// bad[r] = kind_bad of request q0 + r, from the packed kind bytes; returns whether any fails
+__device__ __forceinline__ bool quad_bad(uint32_t k4, uint32_t okset, uint32_t q0, uint32_t Q1, uint32_t (&bad)[4]) {
+#pragma unroll
+    for (uint32_t r = 0; r < 4; r++) bad[r] = kind_bad(okset, (k4 >> (8u * r)) & 0xFFu, q0 + r < Q1);
+    return (bad[0] | bad[1] | bad[2] | bad[3]) != 0;
+}
+// the same from four byte loads of column col (the writers that take the kinds one byte at a time)
+__device__ __forceinline__ bool quad_bad_bytes(const mxp_kargs& A, uint32_t col, uint32_t okset, uint32_t q0,
+                                               uint32_t (&bad)[4]) {
+#pragma unroll
+    for (uint32_t r = 0; r < 4; r++) {
+        const bool in = q0 + r < A.q1;
+        bad[r] = kind_bad(okset, in ? A.kinds[(uint64_t)col * A.n + q0 + r] : 0u, in);
+    }
+    return (bad[0] | bad[1] | bad[2] | bad[3]) != 0;
+}
+// error records of group G (rules `mask`) for the quad's requests that failed the type check
+__device__ __forceinline__ void log_quad_errors(const mxp_kargs& A, uint32_t mask, uint32_t G, const uint32_t (&bad)[4],
+                                                uint32_t q0) {
+    for (uint32_t r = 0; r < 4; r++)
+        if (bad[r] && q0 + r < A.q1) log_guard_errors(A, mask, G * 32u, q0 + r);
+}
+// A failed type check errs every rule of the chunk's groups: writes the error records and returns
+// whether the failed requests get their error flag (req_err wanted, and the chunk has a guarded rule)
+__device__ __forceinline__ bool guard_errors(const mxp_kargs& A, uint32_t g0, uint32_t n, uint32_t moff,
+                                             const uint32_t (&bad)[4], bool any, uint32_t q0) {
+    uint32_t masks = 0;
+    if (A.req_err && any)
+        for (uint32_t g = 0; g < n; g++) masks |= uni(A.fill_masks[moff + g]);
+    if (A.errlog && any)
+        for (uint32_t g = 0; g < n; g++) log_quad_errors(A, uni(A.fill_masks[moff + g]), g0 + g, bad, q0);
+    return masks != 0;
+}
+__device__ __forceinline__ void report_guard_errors(const mxp_kargs& A, uint32_t g0, uint32_t n, uint32_t moff,
+                                                    const uint32_t (&bad)[4], bool any, uint32_t q0) {
+    if (guard_errors(A, g0, n, moff, bad, any, q0))
+        for (uint32_t r = 0; r < 4; r++)
+            if (bad[r] && q0 + r < A.q1) A.req_err[q0 + r] = 1;
+}
+// The quad's four match and four error words at word `at` of each plane (null: not wanted): one
+// 16-byte store per plane where vec (quads_vec), else word by word up to Q1.  nt: non-temporal
+// streaming stores (A/B on C2: 0.828 vs 0.867 ms per evaluation, profiles/r1_v15_ab_nt.log)
+__device__ __forceinline__ void store_quad(uint32_t* om, uint32_t* oe, uint64_t at, const uint32_t (&m)[4],
+                                           const uint32_t (&e)[4], bool vec, bool nt, uint32_t q0, uint32_t Q1) {
+    if (vec && q0 < Q1) {
+        const v4u mv = v4u{m[0], m[1], m[2], m[3]}, ev = v4u{e[0], e[1], e[2], e[3]};
+        if (nt) {
+            if (om) __builtin_nontemporal_store(mv, (v4u*)(om + at));
+            if (oe) __builtin_nontemporal_store(ev, (v4u*)(oe + at));
+        } else {
+            if (om) *(v4u*)(om + at) = mv;
+            if (oe) *(v4u*)(oe + at) = ev;
+        }
+    } else {
+        for (uint32_t r = 0; r < 4; r++) {
+            if (q0 + r >= Q1) break;
+            if (om) om[at + r] = m[r];
+            if (oe) oe[at + r] = e[r];
+        }
+    }
+}
+
 // Chunks of uniform indexed groups (vm.h mxp_fill): every word is a function of the guard column's
 // kind alone -- match 0, error = the rules whose type check fails -- so a lane computes it once for
 // each of its requests and streams 16-byte stores over the chunk's groups (1 KB per
@@ -1009,81 +1097,32 @@ extern "C" __global__ __launch_bounds__(256) void mxp_eval_deep_refs_kernel(mxp_
 extern "C" __global__ __launch_bounds__(256) void mxp_fill_kernel(mxp_kargs A) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = uni(threadIdx.x >> 6);
-    const mxp_fill* F = A.fills + blockIdx.y;
-    const uint32_t col = uni(F->col), okset = uni(F->okset), g0 = uni(F->g0), n = uni(F->n), moff = uni(F->moff);
+    const FillChunk C(A.fills + blockIdx.y);
     const uint32_t span = uni(A.fill_span);
     const uint64_t N = A.n;
     const uint32_t Q1 = A.q1;        // chunk end (chunks start at multiples of 1024)
     const uint32_t qw = A.q0 + (blockIdx.x * 4u + wave) * 256u * span;  // the wave's first request
     if (qw >= Q1) return;
     const uint32_t q0 = qw + lane * 4u;
-    const bool vec = (N & 3u) == 0 && (Q1 & 3u) == 0;  // rows 16-byte aligned, the lane's 4 requests all present
-    uint32_t bad[MXP_FILL_SPAN_MAX][4];  // per request: ~0 when the guard column fails its type check
-    uint32_t any = 0;
+    const bool vec = quads_vec(A);
+    uint32_t bad[MXP_FILL_SPAN_MAX][4] = {};  // per request: ~0 when the guard column fails its type check
+    bool any[MXP_FILL_SPAN_MAX] = {};
 #pragma unroll
-    for (uint32_t sp = 0; sp < MXP_FILL_SPAN_MAX; sp++) {
-        const uint32_t q = q0 + sp * 256u;
-        if (sp < span && vec && q < Q1) {
-            const uint32_t k4 = *(const uint32_t*)(A.kinds + (uint64_t)col * N + q);
-#pragma unroll
-            for (int r = 0; r < 4; r++) bad[sp][r] = ((okset >> ((k4 >> (8 * r)) & 0xFFu)) & 1u) ? 0u : ~0u;
-        } else {
-#pragma unroll
-            for (int r = 0; r < 4; r++) {
-                const bool in = sp < span && q + r < Q1;
-                const uint32_t k = in ? A.kinds[(uint64_t)col * N + q + r] : 0u;
-                bad[sp][r] = (in && !((okset >> k) & 1u)) ? ~0u : 0u;
-            }
-        }
-        any |= bad[sp][0] | bad[sp][1] | bad[sp][2] | bad[sp][3];
-    }
-    if (A.req_err && any) {  // a failed type check errs every rule of the chunk's groups
-        uint32_t masks = 0;
-        for (uint32_t g = 0; g < n; g++) masks |= uni(A.fill_masks[moff + g]);
-        if (masks)
-            for (uint32_t sp = 0; sp < span; sp++)
-                for (uint32_t r = 0; r < 4; r++)
-                    if (bad[sp][r] && q0 + sp * 256u + r < Q1) A.req_err[q0 + sp * 256u + r] = 1;
-    }
-    if (A.errlog && any) {
-        for (uint32_t g = 0; g < n; g++) {
-            const uint32_t mask = uni(A.fill_masks[moff + g]);
-            for (uint32_t sp = 0; sp < span; sp++)
-                for (uint32_t r = 0; r < 4; r++)
-                    if (bad[sp][r] && q0 + sp * 256u + r < Q1) log_guard_errors(A, mask, (g0 + g) * 32u, q0 + sp * 256u + r);
-        }
-    }
-    // non-temporal streaming stores (A/B on C2: 0.828 vs 0.867 ms per evaluation,
-    // profiles/r1_v15_ab_nt.log); MXP_DEBUG_FLAGS 128 = plain stores (ablation)
-    const bool nt = !(A.flags & 128u);
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-    for (uint32_t g = 0; g < n; g++) {
-        const uint32_t mask = uni(A.fill_masks[moff + g]);
-        const uint64_t row = (uint64_t)(g0 + g) * N;
+    for (uint32_t sp = 0; sp < MXP_FILL_SPAN_MAX; sp++)
+        if (sp < span) any[sp] = quad_bad(quad_kinds(A, C.col, q0 + sp * 256u, vec), C.okset, q0 + sp * 256u, Q1, bad[sp]);
+    for (uint32_t sp = 0; sp < span; sp++)
+        report_guard_errors(A, C.g0, C.n, C.moff, bad[sp], any[sp], q0 + sp * 256u);
+    const bool nt = !(A.flags & MXP_DBG_PLAIN_STORES);
+    const uint32_t zero[4] = {0u, 0u, 0u, 0u};
+    for (uint32_t g = 0; g < C.n; g++) {
+        const uint32_t mask = uni(A.fill_masks[C.moff + g]);
+        const uint64_t row = (uint64_t)(C.g0 + g) * N;
 #pragma unroll
         for (uint32_t sp = 0; sp < MXP_FILL_SPAN_MAX; sp++) {
             const uint32_t q = q0 + sp * 256u;
             if (sp >= span || qw + sp * 256u >= Q1) break;  // wave-uniform
-            const uint64_t at = row + q;
-            if (vec) {
-                const v4u m = v4u{0u, 0u, 0u, 0u};
-                const v4u er = v4u{bad[sp][0] & mask, bad[sp][1] & mask, bad[sp][2] & mask, bad[sp][3] & mask};
-                if (q < Q1) {
-                    if (nt) {
-                        if (A.out_match) __builtin_nontemporal_store(m, (v4u*)(A.out_match + at));
-                        if (A.out_err) __builtin_nontemporal_store(er, (v4u*)(A.out_err + at));
-                    } else {
-                        if (A.out_match) *(v4u*)(A.out_match + at) = m;
-                        if (A.out_err) *(v4u*)(A.out_err + at) = er;
-                    }
-                }
-            } else {
-                for (uint32_t r = 0; r < 4; r++) {
-                    if (q + r >= Q1) break;
-                    if (A.out_match) A.out_match[at + r] = 0u;
-                    if (A.out_err) A.out_err[at + r] = bad[sp][r] & mask;
-                }
-            }
+            const uint32_t er[4] = {bad[sp][0] & mask, bad[sp][1] & mask, bad[sp][2] & mask, bad[sp][3] & mask};
+            store_quad(A.out_match, A.out_err, row + q, zero, er, vec, nt, q, Q1);
         }
     }
 }
@@ -1461,12 +1500,12 @@ template <bool kLds>
 __device__ __forceinline__ void vtfill_wave(const mxp_kargs& A, const mxp_fill* F, uint32_t chunk, uint32_t qw,
                                             const uint2* S, const uint32_t* RW) {
     const uint32_t lane = threadIdx.x & 63u;
-    const uint32_t col = uni(F->col), okset = uni(F->okset), g0 = uni(F->g0), n = uni(F->n), moff = uni(F->moff);
+    const FillChunk C(F);
     const uint64_t N = A.n;
     const uint32_t Q1 = A.q1;
     if (qw >= Q1) return;
     const uint32_t q0 = qw + lane * 4u;
-    const bool vec = (N & 3u) == 0 && (Q1 & 3u) == 0 && (q0 & 3u) == 0;
+    const bool vec = quads_vec(A);
     const uint32_t nvt = uni(A.n_vt);
     uint32_t bad[4];
     // 4 x u16 classes per active column, as (lo, hi) u32 pairs of one register vector: a merge
@@ -1474,51 +1513,42 @@ __device__ __forceinline__ void vtfill_wave(const mxp_kargs& A, const mxp_fill* 
     // (s_set_gpr_idx_on) instead of a select over every slot
     typedef uint32_t vcls __attribute__((ext_vector_type(2 * MXP_VT_MAX)));
     vcls clv;
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const bool in = q0 + r < Q1;
-        const uint32_t k = in ? A.kinds[(uint64_t)col * N + q0 + r] : 0u;
-        bad[r] = (in && !((okset >> k) & 1u)) ? ~0u : 0u;
-    }
+    const bool any = quad_bad_bytes(A, C.col, C.okset, q0, bad);
 #pragma unroll
     for (uint32_t a = 0; a < MXP_VT_MAX; a++) {
         uint64_t c = 0;
         if (a < nvt) {
-            const uint16_t* C = A.vt_cls + (uint64_t)a * MXP_VT_PITCH(N);
+            const uint16_t* cls = A.vt_cls + (uint64_t)a * MXP_VT_PITCH(N);
             if (vec && q0 < Q1) {
-                c = *(const uint64_t*)(C + q0);
+                c = *(const uint64_t*)(cls + q0);
             } else {
                 for (uint32_t r = 0; r < 4; r++)
-                    if (q0 + r < Q1) c |= (uint64_t)C[q0 + r] << (16u * r);
+                    if (q0 + r < Q1) c |= (uint64_t)cls[q0 + r] << (16u * r);
             }
         }
         clv[2 * a] = (uint32_t)c;
         clv[2 * a + 1] = (uint32_t)(c >> 32);
     }
-    const bool any = (bad[0] | bad[1] | bad[2] | bad[3]) != 0;
     DtpQueue dq;
     dq.load(A, chunk, q0, q0 < Q1);
     const bool dany = __ballot(dq.q0 != ~0u) != 0;
-    const bool nt = !(A.flags & 128u);
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    const bool nt = !(A.flags & MXP_DBG_PLAIN_STORES);
     // the active slots' (cap, tbase), the chunk's group masks and merge entries: one vector load
     // each, read back with v_readlane -- no chain of dependent scalar loads per group
     const uint32_t MV = lane < 2u * MXP_VT_MAX && (lane >> 1) < nvt ? A.vt_meta[(lane >> 1) * 8u + MXP_VTM_CAP + (lane & 1u)] : 0u;
-    const uint32_t FM = lane < n ? A.fill_masks[moff + lane] : 0u;
-    const uint32_t GM = kLds && lane < n ? A.gvt_mask[g0 + lane] : 0u;  // slots each group names
-    const uint32_t GO = lane <= n ? A.gvt_off[g0 + lane] : 0u;
-    const uint32_t e0 = __builtin_amdgcn_readlane(GO, 0), ecount = __builtin_amdgcn_readlane(GO, n) - e0;
+    const uint32_t FM = lane < C.n ? A.fill_masks[C.moff + lane] : 0u;
+    const uint32_t GM = kLds && lane < C.n ? A.gvt_mask[C.g0 + lane] : 0u;  // slots each group names
+    const uint32_t GO = lane <= C.n ? A.gvt_off[C.g0 + lane] : 0u;
+    const uint32_t e0 = __builtin_amdgcn_readlane(GO, 0), ecount = __builtin_amdgcn_readlane(GO, C.n) - e0;
     uint32_t GE0 = lane < ecount ? A.gvt[e0 + lane] : 0u, GE1 = lane + 64u < ecount ? A.gvt[e0 + 64u + lane] : 0u;
     uint32_t anyerr[4] = {0u, 0u, 0u, 0u};
-    for (uint32_t g = 0; g < n; g++) {
-        const uint32_t G = g0 + g;
+    for (uint32_t g = 0; g < C.n; g++) {
+        const uint32_t G = C.g0 + g;
         const uint32_t mask = __builtin_amdgcn_readlane(FM, g);
         uint32_t m[4] = {0u, 0u, 0u, 0u}, e[4], ve[4] = {0u, 0u, 0u, 0u};
 #pragma unroll
         for (int r = 0; r < 4; r++) e[r] = bad[r] & mask;
-        if (A.errlog && any && mask)
-            for (uint32_t r = 0; r < 4; r++)
-                if (e[r] && q0 + r < Q1) log_guard_errors(A, e[r], G * 32u, q0 + r);
+        if (A.errlog && any && mask) log_quad_errors(A, mask, G, bad, q0);
         const uint32_t i0 = __builtin_amdgcn_readlane(GO, g) - e0, i1 = __builtin_amdgcn_readlane(GO, g + 1) - e0;
         if constexpr (kLds) {
             // staged (<= 128 entries): the group's entries in slot order, one per slot it names --
@@ -1546,24 +1576,14 @@ __device__ __forceinline__ void vtfill_wave(const mxp_kargs& A, const mxp_fill* 
             const uint32_t a = ent >> 24, j = ent & 0xFFFFFFu;
             const uint32_t au = __builtin_amdgcn_readfirstlane(a);
             const uint64_t c = (uint64_t)clv[2u * au] | (uint64_t)clv[2u * au + 1u] << 32;
-            if constexpr (kLds) {
-                const uint32_t row = j;  // (the entry's LDS row, computed above; staged chunks have <= 128 entries)
+            const uint32_t cap = __builtin_amdgcn_readlane(MV, 2u * a);
+            const uint32_t tb = __builtin_amdgcn_readlane(MV, 2u * a + 1u);
+            const uint64_t row = (uint64_t)tb + (uint64_t)j * cap;
 #pragma unroll
-                for (uint32_t r = 0; r < 4; r++) {
-                    const uint2 w = S[row + ((uint32_t)(c >> (16u * r)) & 0xFFFFu)];
-                    m[r] |= w.x;
-                    ve[r] |= w.y;
-                }
-            } else {
-                const uint32_t cap = __builtin_amdgcn_readlane(MV, 2u * a);
-                const uint32_t tb = __builtin_amdgcn_readlane(MV, 2u * a + 1u);
-                const uint64_t row = (uint64_t)tb + (uint64_t)j * cap;
-#pragma unroll
-                for (uint32_t r = 0; r < 4; r++) {
-                    const uint2 w = *(const uint2*)(A.vt_tm + 2u * (row + ((c >> (16u * r)) & 0xFFFFu)));
-                    m[r] |= w.x;
-                    ve[r] |= w.y;
-                }
+            for (uint32_t r = 0; r < 4; r++) {
+                const uint2 w = *(const uint2*)(A.vt_tm + 2u * (row + ((c >> (16u * r)) & 0xFFFFu)));
+                m[r] |= w.x;
+                ve[r] |= w.y;
             }
         }
         uint32_t vmask[4];
@@ -1583,24 +1603,7 @@ __device__ __forceinline__ void vtfill_wave(const mxp_kargs& A, const mxp_fill* 
         // mxp_vt_eval_kernel counts per class)
 #pragma unroll
         for (uint32_t r = 0; r < 4; r++) anyerr[r] |= e[r];  // (request error flags: once, after the loop)
-        const uint64_t at = (uint64_t)G * N + q0;
-        if (vec && q0 < Q1) {
-            const v4u mv = v4u{m[0], m[1], m[2], m[3]};
-            const v4u ev = v4u{e[0], e[1], e[2], e[3]};
-            if (nt) {
-                if (A.out_match) __builtin_nontemporal_store(mv, (v4u*)(A.out_match + at));
-                if (A.out_err) __builtin_nontemporal_store(ev, (v4u*)(A.out_err + at));
-            } else {
-                if (A.out_match) *(v4u*)(A.out_match + at) = mv;
-                if (A.out_err) *(v4u*)(A.out_err + at) = ev;
-            }
-        } else {
-            for (uint32_t r = 0; r < 4; r++) {
-                if (q0 + r >= Q1) break;
-                if (A.out_match) A.out_match[at + r] = m[r];
-                if (A.out_err) A.out_err[at + r] = e[r];
-            }
-        }
+        store_quad(A.out_match, A.out_err, (uint64_t)G * N + q0, m, e, vec, nt, q0, Q1);
     }
     if (A.req_err)
         for (uint32_t r = 0; r < 4; r++)
@@ -1613,33 +1616,16 @@ __device__ __forceinline__ void fill_dtp_groups(const mxp_kargs& A, uint32_t g0,
                                                 const uint32_t (&bad)[4], DtpQueue& dq, uint32_t q0) {
     const uint64_t N = A.n;
     const uint32_t Q1 = A.q1;
-    const bool vec = (N & 3u) == 0 && (Q1 & 3u) == 0;
+    const bool vec = quads_vec(A);
     const bool dany = __ballot(dq.q0 != ~0u) != 0;
-    const bool nt = !(A.flags & 128u);
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
+    const bool nt = !(A.flags & MXP_DBG_PLAIN_STORES);
     for (uint32_t g = 0; g < n; g++) {
         const uint32_t mask = uni(A.fill_masks[moff + g]);
         uint32_t m[4] = {0u, 0u, 0u, 0u}, e[4];
 #pragma unroll
         for (int r = 0; r < 4; r++) e[r] = bad[r] & mask;
         if (dany) dq.merge(g, m, e);
-        const uint64_t at = (uint64_t)(g0 + g) * N + q0;
-        if (vec && q0 < Q1) {
-            const v4u mv = v4u{m[0], m[1], m[2], m[3]}, ev = v4u{e[0], e[1], e[2], e[3]};
-            if (nt) {
-                if (A.out_match) __builtin_nontemporal_store(mv, (v4u*)(A.out_match + at));
-                if (A.out_err) __builtin_nontemporal_store(ev, (v4u*)(A.out_err + at));
-            } else {
-                if (A.out_match) *(v4u*)(A.out_match + at) = mv;
-                if (A.out_err) *(v4u*)(A.out_err + at) = ev;
-            }
-        } else {
-            for (uint32_t r = 0; r < 4; r++) {
-                if (q0 + r >= Q1) break;
-                if (A.out_match) A.out_match[at + r] = m[r];
-                if (A.out_err) A.out_err[at + r] = e[r];
-            }
-        }
+        store_quad(A.out_match, A.out_err, (uint64_t)(g0 + g) * N + q0, m, e, vec, nt, q0, Q1);
     }
 }
 
@@ -1648,39 +1634,19 @@ __device__ __forceinline__ void fill_dtp_groups(const mxp_kargs& A, uint32_t g0,
 extern "C" __global__ __launch_bounds__(256) void mxp_fill_dtp_kernel(mxp_kargs A) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = uni(threadIdx.x >> 6);
-    const mxp_fill* F = A.fills + blockIdx.y;
-    const uint32_t col = uni(F->col), okset = uni(F->okset), g0 = uni(F->g0), n = uni(F->n), moff = uni(F->moff);
-    const uint64_t N = A.n;
+    const FillChunk C(A.fills + blockIdx.y);
     const uint32_t Q1 = A.q1;
     const uint32_t qw = A.q0 + (blockIdx.x * 4u + wave) * 256u;
     if (qw >= Q1) return;
     const uint32_t q0 = qw + lane * 4u;
     uint32_t bad[4];
-#pragma unroll
-    for (int r = 0; r < 4; r++) {
-        const bool in = q0 + r < Q1;
-        const uint32_t k = in ? A.kinds[(uint64_t)col * N + q0 + r] : 0u;
-        bad[r] = (in && !((okset >> k) & 1u)) ? ~0u : 0u;
-    }
-    const bool any = (bad[0] | bad[1] | bad[2] | bad[3]) != 0;
+    const bool any = quad_bad_bytes(A, C.col, C.okset, q0, bad);
     // (a pair Resolve's evaluation: only the request error flags and records unless pairs overflowed)
     const bool store = !A.dtp_lazy || uni(*A.dtp_lazy) != 0u;
     DtpQueue dq;
     if (store) dq.load(A, A.dtp_cbase + blockIdx.y, q0, q0 < Q1);
-    if (A.req_err && any) {
-        uint32_t masks = 0;
-        for (uint32_t g = 0; g < n; g++) masks |= uni(A.fill_masks[moff + g]);
-        if (masks)
-            for (uint32_t r = 0; r < 4; r++)
-                if (bad[r] && q0 + r < Q1) A.req_err[q0 + r] = 1;
-    }
-    if (A.errlog && any)
-        for (uint32_t g = 0; g < n; g++) {
-            const uint32_t mask = uni(A.fill_masks[moff + g]);
-            for (uint32_t r = 0; r < 4; r++)
-                if (bad[r] && q0 + r < Q1) log_guard_errors(A, mask, (g0 + g) * 32u, q0 + r);
-        }
-    if (store) fill_dtp_groups(A, g0, n, moff, bad, dq, q0);
+    report_guard_errors(A, C.g0, C.n, C.moff, bad, any, q0);
+    if (store) fill_dtp_groups(A, C.g0, C.n, C.moff, bad, dq, q0);
 }
 
 // One live item of the retained-bitmap fill: quad `quad` of the tile (first request qt) in plain
@@ -1692,7 +1658,6 @@ extern "C" __global__ __launch_bounds__(256) void mxp_fill_dtp_kernel(mxp_kargs 
 // Plain stores: a lone 16-byte row gains nothing from bypassing the cache (MXP_DEBUG_FLAGS 4194304:
 // non-temporal)
 struct FillTileItem {
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
     v4u sc, sp;
     uint32_t g0, n, dkc = 0u, dkp = 0u, q0;
     // e: chunk << 16 | quad << 8 | current count << 4 | previous count
@@ -1712,8 +1677,8 @@ struct FillTileItem {
         const uint64_t N = A.n;
         const uint32_t Q1 = A.q1;
         if (!(dkc | dkp) || q0 >= Q1) return;  // (no pair is filed past the batch: defensive)
-        const bool vec = (N & 3u) == 0 && (Q1 & 3u) == 0;
-        const bool snt = (A.flags & 4194304u) != 0u;
+        const bool vec = quads_vec(A);
+        const bool snt = (A.flags & MXP_DBG_TILE_NT_STORES) != 0u;
         DtpQueue dq, dp;
         dq.decode(dkc, sc);
         dp.decode(dkp, sp);
@@ -1724,19 +1689,7 @@ struct FillTileItem {
             uint32_t m[4] = {0u, 0u, 0u, 0u}, z[4] = {0u, 0u, 0u, 0u};
             const bool cur = dq.take(g, m);
             const bool was = dp.take(g, z);
-            if (cur || was) {
-                const uint64_t at = (uint64_t)(g0 + g) * N + q0;
-                if (vec) {
-                    const v4u mv = v4u{m[0], m[1], m[2], m[3]};
-                    if (snt)
-                        __builtin_nontemporal_store(mv, (v4u*)(A.out_match + at));
-                    else
-                        *(v4u*)(A.out_match + at) = mv;
-                } else {
-                    for (uint32_t r = 0; r < 4; r++)
-                        if (q0 + r < Q1) A.out_match[at + r] = m[r];
-                }
-            }
+            if (cur || was) store_quad(A.out_match, nullptr, (uint64_t)(g0 + g) * N + q0, m, m, vec, snt, q0, Q1);
         }
     }
 };
@@ -1758,7 +1711,6 @@ struct FillTileItem {
 #define MXP_FTQ 8u
 extern "C" __global__ __launch_bounds__(256) void mxp_fill_tile_kernel(mxp_kargs A, uint32_t n_fills) {
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = uni(tid >> 6);
-    const uint64_t N = A.n;
     const uint32_t Q1 = A.q1;
     const uint32_t qt = A.q0 + blockIdx.x * 1024u;  // (a multiple of 1024: mxp_launch_fill)
     if (qt >= Q1) return;
@@ -1777,7 +1729,7 @@ extern "C" __global__ __launch_bounds__(256) void mxp_fill_tile_kernel(mxp_kargs
     };
     if (!dense) load_counts(0u);
     {
-        const bool kvec = (N & 3u) == 0 && ((uintptr_t)A.kinds & 3u) == 0;
+        const bool vec = quads_vec(A);
         uint32_t col = ~0u, okset = 0u, kb = 0u, bad[4] = {0u, 0u, 0u, 0u}, flagged = 0u;
         bool any = false;
         for (uint32_t f0 = 0; f0 < n_fills; f0 += 64u) {
@@ -1786,43 +1738,18 @@ extern "C" __global__ __launch_bounds__(256) void mxp_fill_tile_kernel(mxp_kargs
             const uint32_t f1 = min(64u, n_fills - f0);
             for (uint32_t i = 0; i < f1; i++) {
                 const uint32_t c = __builtin_amdgcn_readlane(colv, i), ok = __builtin_amdgcn_readlane(okv, i);
-                if (c != col) {  // the quad's four kind bytes
-                    kb = 0u;
-                    if (kvec) {
-                        if (q0 < Q1) kb = *(const uint32_t*)(A.kinds + (uint64_t)c * N + q0);
-                    } else {
-                        for (uint32_t r = 0; r < 4; r++)
-                            if (q0 + r < Q1) kb |= (uint32_t)A.kinds[(uint64_t)c * N + q0 + r] << (8u * r);
-                    }
-                }
-                if (c != col || ok != okset) {
-#pragma unroll
-                    for (uint32_t r = 0; r < 4; r++)
-                        bad[r] = (q0 + r < Q1 && !((ok >> ((kb >> (8u * r)) & 0xFFu)) & 1u)) ? ~0u : 0u;
-                    any = (bad[0] | bad[1] | bad[2] | bad[3]) != 0;
-                }
+                if (c != col) kb = quad_kinds(A, c, q0, vec);
+                if (c != col || ok != okset) any = quad_bad(kb, ok, q0, Q1, bad);
                 col = c;
                 okset = ok;
                 if (!dense && !__ballot(any)) continue;  // (the chunk's groups: only where they are used)
                 const mxp_fill* F = A.fills + f0 + i;
                 const uint32_t g0 = uni(F->g0), n = uni(F->n), moff = uni(F->moff);
-                if (A.req_err && any) {
-                    uint32_t masks = 0;
-                    for (uint32_t g = 0; g < n; g++) masks |= uni(A.fill_masks[moff + g]);
-                    if (masks)
-                        for (uint32_t r = 0; r < 4; r++) flagged |= bad[r] & (1u << r);
-                }
-                // (error records, as the dense fill writes them.  No evaluation reaches this branch
-                // today: only a caller's buffer can be retained, and every entry point that evaluates
-                // into a caller's buffer -- mxp_eval_device*, the group -- runs without records; the
-                // evaluations that log write the engine's own bitmaps.  Kept so that kargs mean the
-                // same in both fills.)
-                if (A.errlog && any)
-                    for (uint32_t g = 0; g < n; g++) {
-                        const uint32_t mask = uni(A.fill_masks[moff + g]);
-                        for (uint32_t r = 0; r < 4; r++)
-                            if (bad[r] && q0 + r < Q1) log_guard_errors(A, mask, (g0 + g) * 32u, q0 + r);
-                    }
+                // (the flags are written once, after the walk.  No evaluation into a retained buffer
+                // logs error records today -- only a caller's buffer can be retained, and mxp_eval_device*
+                // and the group run without records -- but the shared report writes them all the same.)
+                if (guard_errors(A, g0, n, moff, bad, any, q0))
+                    for (uint32_t r = 0; r < 4; r++) flagged |= bad[r] & (1u << r);
                 if (dense) {
                     DtpQueue dq;
                     dq.load(A, A.dtp_cbase + f0 + i, q0, q0 < Q1);
@@ -1912,7 +1839,7 @@ extern "C" __global__ __launch_bounds__(256) void mxp_vtfill_lds_kernel(mxp_karg
         }
         total += rows * __builtin_amdgcn_readlane(capl, a);
     }
-    const bool staged = ecount <= 128u && n <= MXP_FILL_CHUNK && total <= MXP_VTF_STAGE && !(A.flags & 2097152u);
+    const bool staged = ecount <= 128u && n <= MXP_FILL_CHUNK && total <= MXP_VTF_STAGE && !(A.flags & MXP_DBG_VTFILL_GLOBAL);
     // the LDS row of every (group, slot) merge entry of the chunk, so the group loop reads them with
     // two broadcast LDS loads per group and no scalar arithmetic (the scalar unit, one per CU,
     // bounded this kernel)
@@ -1995,8 +1922,7 @@ __device__ __forceinline__ void vtfill_imm_body(const mxp_kargs& A, uint32_t bx,
     if constexpr (kSlow) {
         if (!__syncthreads_or(tid < MXP_VTF_TILES * 4u ? slow[tid] : 0)) return;
     }
-    const mxp_fill* F = A.fills + by;
-    const uint32_t col = uni(F->col), okset = uni(F->okset), g0 = uni(F->g0), n = uni(F->n), moff = uni(F->moff);
+    const FillChunk C(A.fills + by);
     const uint32_t chunk = A.dtp_cbase + by;
     // 1. staging: zero, then each (group, slot) merge entry's 64 class words into its fixed row
     for (uint32_t i = tid; i < NVT * MXP_FILL_CHUNK * MXP_VTI_CAP; i += 256u) SM[i] = 0u;
@@ -2005,8 +1931,8 @@ __device__ __forceinline__ void vtfill_imm_body(const mxp_kargs& A, uint32_t bx,
     __syncthreads();
     const uint32_t TB = lane < NVT ? A.vt_meta[lane * 8u + MXP_VTM_TBASE] : 0u;
     uint32_t eor = 0u;
-    for (uint32_t g = 0; g < n; g++) {
-        const uint32_t i0 = uni(A.gvt_off[g0 + g]), i1 = uni(A.gvt_off[g0 + g + 1u]);
+    for (uint32_t g = 0; g < C.n; g++) {
+        const uint32_t i0 = uni(A.gvt_off[C.g0 + g]), i1 = uni(A.gvt_off[C.g0 + g + 1u]);
         for (uint32_t x = tid; x < (i1 - i0) * MXP_VTI_CAP; x += 256u) {
             const uint32_t ent = A.gvt[i0 + x / MXP_VTI_CAP], a = ent >> 24, j = ent & 0xFFFFFFu, k = x % MXP_VTI_CAP;
             const uint32_t tb = __builtin_amdgcn_ds_bpermute((int)(a << 2), (int)TB);
@@ -2023,9 +1949,9 @@ __device__ __forceinline__ void vtfill_imm_body(const mxp_kargs& A, uint32_t bx,
     const bool errs = eflag != 0u;
     const uint64_t N = A.n;
     const uint32_t Q1 = A.q1;
-    const bool nt = !(A.flags & 128u);
-    typedef uint32_t v4u __attribute__((ext_vector_type(4)));
-    const uint32_t FM = lane < n ? A.fill_masks[moff + lane] : 0u;
+    const bool nt = !(A.flags & MXP_DBG_PLAIN_STORES);
+    const bool vec = quads_vec(A);
+    const uint32_t FM = lane < C.n ? A.fill_masks[C.moff + lane] : 0u;
     // A wave-tile's inputs: the guard column's kinds, the classes per slot, the deferred-pair queue's
     // count and slot row.  The fast kernel loads tile t + 1's while tile t's words are stored: its
     // loads then wait only for themselves, not for the tile's 16 stores ahead of them in the
@@ -2037,23 +1963,16 @@ __device__ __forceinline__ void vtfill_imm_body(const mxp_kargs& A, uint32_t bx,
     };
     auto fetch = [&](uint32_t t, TileIn& T) __attribute__((always_inline)) {
         const uint32_t q0 = A.q0 + ((bx * MXP_VTF_TILES + t) * 4u + wave) * 256u + lane * 4u;
-        const bool vec = (N & 3u) == 0 && (Q1 & 3u) == 0 && (q0 & 3u) == 0;
-        T.k4 = 0u;
-        if (vec && q0 < Q1) {
-            T.k4 = *(const uint32_t*)(A.kinds + (uint64_t)col * N + q0);
-        } else {
-            for (uint32_t r = 0; r < 4; r++)
-                if (q0 + r < Q1) T.k4 |= (uint32_t)A.kinds[(uint64_t)col * N + q0 + r] << (8u * r);
-        }
+        T.k4 = quad_kinds(A, C.col, q0, vec);
 #pragma unroll
         for (uint32_t a = 0; a < NVT; a++) {
-            const uint16_t* C = A.vt_cls + (uint64_t)a * MXP_VT_PITCH(N);
+            const uint16_t* cls = A.vt_cls + (uint64_t)a * MXP_VT_PITCH(N);
             uint64_t c = 0;
             if (vec && q0 < Q1) {
-                c = *(const uint64_t*)(C + q0);
+                c = *(const uint64_t*)(cls + q0);
             } else {
                 for (uint32_t r = 0; r < 4; r++)
-                    if (q0 + r < Q1) c |= (uint64_t)C[q0 + r] << (16u * r);
+                    if (q0 + r < Q1) c |= (uint64_t)cls[q0 + r] << (16u * r);
             }
             T.c[a] = c;
         }
@@ -2084,14 +2003,8 @@ __device__ __forceinline__ void vtfill_imm_body(const mxp_kargs& A, uint32_t bx,
         // spilled scalar registers)
         uint64_t Nt = N;
         asm volatile("" : "+s"(Nt));
-        const bool vec = (N & 3u) == 0 && (Q1 & 3u) == 0 && (q0 & 3u) == 0;
         uint32_t bad[4];
-#pragma unroll
-        for (uint32_t r = 0; r < 4; r++) {
-            const bool in = q0 + r < Q1;
-            const uint32_t k = (cur.k4 >> (8u * r)) & 0xFFu;
-            bad[r] = (in && !((okset >> k) & 1u)) ? ~0u : 0u;
-        }
+        const bool any = quad_bad(cur.k4, C.okset, q0, Q1, bad);
         // each request's byte address per slot: [a][g = 0][its class] (kept in registers: the
         // unrolled groups add only an immediate offset)
         uint32_t adb[NVT][4];
@@ -2100,7 +2013,6 @@ __device__ __forceinline__ void vtfill_imm_body(const mxp_kargs& A, uint32_t bx,
 #pragma unroll
             for (uint32_t r = 0; r < 4; r++)
                 adb[a][r] = 4u * (a * MXP_FILL_CHUNK * MXP_VTI_CAP + ((uint32_t)(cur.c[a] >> (16u * r)) & (MXP_VTI_CAP - 1u)));
-        const bool any = (bad[0] | bad[1] | bad[2] | bad[3]) != 0;
         const bool wbad = __ballot(any) != 0;
         DtpQueue dq;
         dq.decode(cur.dk, cur.sl);
@@ -2117,16 +2029,14 @@ __device__ __forceinline__ void vtfill_imm_body(const mxp_kargs& A, uint32_t bx,
         auto group = [&](auto gc) __attribute__((always_inline)) {
             constexpr bool ct = decltype(gc)::ct;
             const uint32_t g = gc.value;
-            if (ct && g >= n) return;  // (a rule set's last chunk: fewer groups)
-            const uint32_t G = g0 + g;
+            if (ct && g >= C.n) return;  // (a rule set's last chunk: fewer groups)
+            const uint32_t G = C.g0 + g;
             uint32_t m[4] = {0u, 0u, 0u, 0u}, e[4] = {0u, 0u, 0u, 0u};
             if constexpr (!ct) {
                 const uint32_t mask = __builtin_amdgcn_readlane(FM, g);
 #pragma unroll
                 for (int r = 0; r < 4; r++) e[r] = bad[r] & mask;
-                if (A.errlog && any && mask)
-                    for (uint32_t r = 0; r < 4; r++)
-                        if (e[r] && q0 + r < Q1) log_guard_errors(A, e[r], G * 32u, q0 + r);
+                if (A.errlog && any && mask) log_quad_errors(A, mask, G, bad, q0);
             }
 #pragma unroll
             for (uint32_t a = 0; a < NVT; a++)
@@ -2162,27 +2072,11 @@ __device__ __forceinline__ void vtfill_imm_body(const mxp_kargs& A, uint32_t bx,
             // (row bases wave-uniform: scalar arithmetic, one address add per store)
             uint32_t* const om = A.out_match ? A.out_match + (uint64_t)G * Nt : nullptr;
             uint32_t* const oe = A.out_err ? A.out_err + (uint64_t)G * Nt : nullptr;
-            if (vec && q0 < Q1) {
-                const v4u mv = v4u{m[0], m[1], m[2], m[3]};
-                const v4u ev = v4u{e[0], e[1], e[2], e[3]};
-                if (nt) {
-                    if (om) __builtin_nontemporal_store(mv, (v4u*)(om + q0));
-                    if (oe) __builtin_nontemporal_store(ev, (v4u*)(oe + q0));
-                } else {
-                    if (om) *(v4u*)(om + q0) = mv;
-                    if (oe) *(v4u*)(oe + q0) = ev;
-                }
-            } else {
-                for (uint32_t r = 0; r < 4; r++) {
-                    if (q0 + r >= Q1) break;
-                    if (om) om[q0 + r] = m[r];
-                    if (oe) oe[q0 + r] = e[r];
-                }
-            }
+            store_quad(om, oe, q0, m, e, vec, nt, q0, Q1);
         };
         if constexpr (kSlow) {
 #pragma nounroll
-            for (uint32_t g = 0; g < n; g++) group(GroupR{g});
+            for (uint32_t g = 0; g < C.n; g++) group(GroupR{g});
         } else {
             const bool to_slow = wbad || errs || derr;
             if (lane == 0) slow[t * 4u + wave] = to_slow ? 1u : 0u;
@@ -2554,7 +2448,7 @@ __device__ __forceinline__ void process_slot(PairQueue& Q, uint32_t tbl, uint32_
             const uint32_t* __restrict__ const tmpl_of = tbl ? A.rule_tmpl2 : A.rule_tmpl;
             const uint32_t* __restrict__ const postings = A.postings;
             const bool post_tmpl = A.post_tmpl != 0u;
-            const bool coop = !(A.flags & 16384u);
+            const bool coop = !(A.flags & MXP_DBG_NO_COOP_LISTS);
             const PairSink S = pair_sink<kDtp>();
             const uint32_t want = j0 < len ? len - j0 : 0u, freeq = MXP_IXQ - Q.n;  // freeq > 192
             const uint32_t before = wave_incl_sum(want, lane) - want;
@@ -2855,7 +2749,7 @@ __device__ __forceinline__ void index_body(uint64_t (*regs)[kS]) {
         ckargs& A = kargs_view();
         const uint32_t n_idx = A.n_idx;
         const uint64_t N = A.n;
-        const bool probes_only = (A.flags & 1024u) != 0u;
+        const bool probes_only = (A.flags & MXP_DBG_PROBES_ONLY) != 0u;
         const uint8_t* const kinds = A.kinds;
         const uint64_t* const vals = A.vals;
         const uint4* const heads = A.heads;
@@ -3270,7 +3164,7 @@ extern "C" hipError_t mxp_launch_eval(const mxp_kargs* args, uint32_t grid_x, ui
         hipLaunchKernelGGL(mxp_eval_nfa_kernel, dim3(grid_x, grid_y), dim3(256), 0, s, *args);
     else if (vm)
         hipLaunchKernelGGL(mxp_eval_kernel, dim3(grid_x, grid_y), dim3(256), 0, s, *args);
-    else if (args->flags & 65536u)
+    else if (args->flags & MXP_DBG_GUARD1)
         hipLaunchKernelGGL(mxp_guard_kernel, dim3(grid_x, grid_y), dim3(256), 0, s, *args);
     else
         hipLaunchKernelGGL(mxp_guard2_kernel, dim3((grid_x + 1) / 2, grid_y), dim3(256), 0, s, *args);
@@ -3301,7 +3195,7 @@ extern "C" hipError_t mxp_launch_fill(const mxp_kargs* args, uint32_t n_fills, h
 }
 
 extern "C" hipError_t mxp_launch_vtfill(const mxp_kargs* args, uint32_t n_fills, hipStream_t s) {
-    if (args->flags & 2097152u) {
+    if (args->flags & MXP_DBG_VTFILL_GLOBAL) {
         hipLaunchKernelGGL(mxp_vtfill_kernel, dim3((args->q1 - args->q0 + 1023u) / 1024u, n_fills), dim3(256), 0, s, *args);
     } else {
         const uint32_t per = 1024u * MXP_VTF_TILES;
@@ -3311,7 +3205,7 @@ extern "C" hipError_t mxp_launch_vtfill(const mxp_kargs* args, uint32_t n_fills,
         // (and its general loop for the wave-tiles it leaves, kargs.vtf_slow)
         void (*k)(mxp_kargs) = mxp_vtfill_lds_kernel;
         void (*ks)(mxp_kargs, uint32_t, uint32_t) = nullptr;
-        if (args->vt_imm && args->vtf_slow && !(args->flags & 33554432u)) {
+        if (args->vt_imm && args->vtf_slow && !(args->flags & MXP_DBG_VTFILL_LDS)) {
             switch (args->n_vt) {
 #define MXP_VTFILL_CASE(K)                  \
     case K:                                 \
@@ -3386,7 +3280,7 @@ extern "C" hipError_t mxp_launch_index(const mxp_kargs* args, uint32_t grid, hip
     else if (args->wave_t)
         hipLaunchKernelGGL(mxp_index_prof_kernel, dim3(grid), dim3(256), 0, s, *args);
     else
-        if (args->flags & 8192u)
+        if (args->flags & MXP_DBG_INDEX5)
             hipLaunchKernelGGL(mxp_index5_kernel, dim3(grid), dim3(256), 0, s, *args);
         else
             hipLaunchKernelGGL(mxp_index_kernel, dim3(grid), dim3(256), 0, s, *args);

@@ -404,7 +404,7 @@ int mxp_engine::pack_device_body(const mxp_bag_batch* b, mxp_dbatch* db) {
     // ---- value classes: distinct values of the candidate columns (read back with the longest
     // string: the one synchronisation of the upload)
     const uint32_t ncand = (uint32_t)std::min<size_t>(vt_cand_col.size(), MXP_PACK_VTCAND);
-    const bool vt_on = !(debug_flags & 131072u) && n && ncand;
+    const bool vt_on = !(debug_flags & MXP_DBG_NO_VT) && n && ncand;
     db->vtd_ready = false;
     if (vt_on) {
         const uint32_t tiles = (uint32_t)((n + MXP_VTD_TILE - 1) / MXP_VTD_TILE);
@@ -566,7 +566,7 @@ int mxp_engine::finish_pack(mxp_dbatch* db) {
     db->vt_capc.assign(vt_cand_col.size(), 0);
     if (db->pk_vt_on) {
         uint32_t active = 0;
-        const bool force = (debug_flags & 262144u) != 0;
+        const bool force = (debug_flags & MXP_DBG_FORCE_VT) != 0;
         db->vtd_ready = true;
         for (uint32_t a = 0; a < db->pk_ncand && active < MXP_VT_MAX; a++) {
             const uint64_t D = meta[2 * a];
@@ -587,7 +587,7 @@ int mxp_engine::finish_pack(mxp_dbatch* db) {
     g_bin_db_size = sizeof(mxp_dbatch);
     int rc = pack_vt_tables(db);
     // (MXP_DEBUG_FLAGS 1 << 29, tests only: the next finish fails here once, after the class tables)
-    if (!rc && (debug_flags & (1u << 29)) && !finish_fail_done) {
+    if (!rc && (debug_flags & MXP_DBG_FINISH_FAIL) && !finish_fail_done) {
         finish_fail_done = true;
         rc = fail(MXP_ERR_NOMEM, "injected finish_pack failure");
     }

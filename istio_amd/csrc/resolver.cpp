@@ -152,8 +152,7 @@ int mxp_resolver_set(mxp_engine* eng, const char* identity_attr, const char* def
 
 namespace {
 
-// MXP_DEBUG_FLAGS: resolve through the error bitmap (the pre-round-5 path), for A/B and tests
-constexpr uint32_t kResolveBitmap = 1u << 28;
+// (MXP_DBG_RESOLVE_BITMAP: resolve through the error bitmap, the pre-round-5 path, for A/B and tests)
 // ids enqueued with the other outputs only for capacities up to this many bytes (the device buffer
 // is sized by the capacity, not the count)
 constexpr uint64_t kEarlyIdsMax = 256ull << 20;
@@ -305,7 +304,7 @@ int resolve_begin(mxp_resolve_job& J) {
         eng->res_tab_key = tab_key;
         eng->res_any_empty = any_empty;
     }
-    J.compact = !J.ref_off && !(eng->debug_flags & kResolveBitmap);
+    J.compact = !J.ref_off && !(eng->debug_flags & MXP_DBG_RESOLVE_BITMAP);
     if (J.compact) {
         if (eng->device >= 0 && (e = eng->res_flags.reserve(n ? n : 1)) != hipSuccess) return eng->hipfail(e, "alloc flags");
         // pair Resolve: the selected rules from the evaluation's deferred pairs, the bitmap left

@@ -133,3 +133,24 @@ def test_go_binding_calls_declared_symbols():
             n_args += ch == "," and depth == 1
             i += 1
         assert n_args == hdr_decl[m.group(1)].count(",") + 1, (m.group(1), go[m.end():i])
+
+
+def test_debug_flags_are_named_single_bits():
+    """MXP_DEBUG_FLAGS: every bit the code tests has a name in one enum (kargs.h MXP_DBG_*), the
+    values are distinct single bits, and no source tests a flag word against a bare number."""
+    csrc = os.path.join(ROOT, "istio_amd", "csrc")
+    enum = re.search(r"enum : uint32_t \{(.*?)\};", open(os.path.join(csrc, "kargs.h")).read(), re.S).group(1)
+    flags = {m.group(1): 1 << int(m.group(2)) for m in re.finditer(r"\b(MXP_DBG_\w+) = 1u << (\d+),\s*//\s*\S", enum)}
+    assert len(flags) >= 26 and len(flags) == len(re.findall(r"MXP_DBG_\w+", enum))  # (each with its comment)
+    assert len(set(flags.values())) == len(flags) and all(v < 1 << 32 for v in flags.values())
+    # the numbers tests, tools and DESIGN.md use
+    assert flags["MXP_DBG_PLAIN_STORES"] == 128 and flags["MXP_DBG_FORCE_VT"] == 262144
+    assert flags["MXP_DBG_VTFILL_GLOBAL"] == 2097152 and flags["MXP_DBG_TILE_NT_STORES"] == 4194304
+    assert flags["MXP_DBG_VTFILL_LDS"] == 33554432 and flags["MXP_DBG_NO_VT"] == 131072
+    used = set()
+    for name in sorted(os.listdir(csrc)):
+        src = open(os.path.join(csrc, name), errors="replace").read()
+        assert not re.search(r"flags & [0-9(]", src), name
+        if name != "kargs.h":
+            used |= set(re.findall(r"MXP_DBG_\w+", src))
+    assert used == set(flags), used ^ set(flags)
