@@ -9,13 +9,15 @@
 //                                       the entry has no '/', net.ParseCIDR; the IPNets become
 //                                       disjoint sorted address intervals (IPNet.Contains per
 //                                       family after To4), so a check is a binary search instead of
-//                                       the reference's linear scan (ipList.go:77-92).
+//                                       the reference's linear scan (ipList.go:77-92).  That host
+//                                       half is cidr.h.
 // Checks run HandleListEntry (list.go:68-101) on the GPU (lists.hip).
 #include <algorithm>
 #include <cstring>
 #include <functional>
 #include <limits>
 
+#include "cidr.h"
 #include "engine_impl.h"
 #include "goupper.h"
 #include "lists.h"
@@ -177,94 +179,6 @@ uint64_t host_hash(const std::string& s, bool upper) {
     return mxp_hash_final(h, s.size());
 }
 
-// net.ParseCIDR (Go 1.9 src/net/ip.go) -> IPNet{IP: ip.Mask(m), Mask: m}; false on ParseError
-struct Net {
-    uint8_t ip[16];
-    int iplen;
-    uint8_t mask[16];
-    int masklen;
-};
-
-bool parse_cidr(const std::string& s, Net* out) {
-    const size_t slash = s.find('/');
-    if (slash == std::string::npos) return false;
-    const uint8_t* a = (const uint8_t*)s.data();
-    uint8_t ip[16];
-    int iplen = 4;
-    if (!mxpnet::parse_v4(a, (uint32_t)slash, ip)) {
-        iplen = 16;
-        if (!mxpnet::parse_v6(a, (uint32_t)slash, ip)) return false;
-    }
-    int n;
-    uint32_t used;
-    const uint8_t* m = a + slash + 1;
-    const uint32_t ml = (uint32_t)(s.size() - slash - 1);
-    if (!mxpnet::dtoi(m, ml, &n, &used) || used != ml || n < 0 || n > 8 * iplen) return false;
-    // CIDRMask(n, 8 * iplen)
-    uint8_t mask[16] = {0};
-    for (int i = 0; i < iplen; i++) {
-        const int bits = std::min(8, std::max(0, n - 8 * i));
-        mask[i] = (uint8_t)(0xFF00u >> bits);
-    }
-    // ip.Mask(m): a 4-byte mask on a v4-in-v6 address masks its last 4 bytes
-    Net r{};
-    r.masklen = iplen;
-    memcpy(r.mask, mask, iplen);
-    const uint8_t* src = ip;
-    int srclen = 16;
-    if (iplen == 4 && mxpnet::is_v4(ip)) {
-        src = ip + 12;
-        srclen = 4;
-    }
-    if (srclen != iplen) return false;  // not reachable from ParseCIDR
-    r.iplen = iplen;
-    for (int i = 0; i < iplen; i++) r.ip[i] = src[i] & mask[i];
-    *out = r;
-    return true;
-}
-
-// networkNumberAndMask (ip.go): the family a net matches after IP.To4, or false (never matches)
-bool net_number_and_mask(const Net& n, uint8_t nn[16], int* nnlen, uint8_t m[16]) {
-    uint8_t ip16[16];
-    const uint8_t* ip = n.ip;
-    int iplen = n.iplen;
-    if (iplen == 16 && mxpnet::is_v4(n.ip)) {  // To4 of a v4-in-v6 network number
-        memcpy(ip16, n.ip + 12, 4);
-        ip = ip16;
-        iplen = 4;
-    }
-    const uint8_t* mk = n.mask;
-    int mlen = n.masklen;
-    if (mlen == 4) {
-        if (iplen != 4) return false;
-    } else if (mlen == 16) {
-        if (iplen == 4) {
-            mk = n.mask + 12;
-            mlen = 4;
-        }
-    } else {
-        return false;
-    }
-    memcpy(nn, ip, iplen);
-    memcpy(m, mk, mlen);
-    *nnlen = iplen;
-    return true;
-}
-
-template <class T>
-void merge(std::vector<std::pair<T, T>>& v) {
-    std::sort(v.begin(), v.end());
-    std::vector<std::pair<T, T>> o;
-    for (auto& p : v) {
-        if (!o.empty() && (p.first <= o.back().second || (o.back().second != std::numeric_limits<T>::max() &&
-                                                          p.first == o.back().second + 1)))
-            o.back().second = std::max(o.back().second, p.second);
-        else
-            o.push_back(p);
-    }
-    v.swap(o);
-}
-
 // IP lists: address families in waves of their own (mxp_list_ip_kernel); MXP_LIST_IP_SPLIT=0: the
 // one-lookup-per-lane kernel (A/B)
 // MXP_LIST_OPT (lists.h MXP_LIST_OPT_*): the IPv4 register parse and the string register window are
@@ -343,41 +257,21 @@ int mxp_list_create(mxp_engine* eng, int entry_type, const char* const* entries,
         if ((rc = put(L->ent_pool, pool.data(), pool.size(), "upload list pool"))) return rc;
     } else if (entry_type == MXP_LIST_IP_ADDRESSES) {
         std::vector<std::pair<uint32_t, uint32_t>> r4;
-        std::vector<std::pair<unsigned __int128, unsigned __int128>> r6;
+        std::vector<std::pair<mxpcidr::u128, mxpcidr::u128>> r6;
         auto add = [&](const std::string& orig, bool strict) -> int {
-            std::string ip = orig;
-            if (ip.find('/') == std::string::npos) ip += "/32";
-            Net n;
-            if (!parse_cidr(ip, &n)) {
+            std::string ip;
+            if (!mxpcidr::add_entry(orig, r4, r6, &ip)) {
                 if (!strict) return MXP_OK;  // overrides: errors ignored (config was validated)
                 return eng->fail(MXP_ERR_ARG, "could not parse list entry " + orig + ": invalid CIDR address: " + ip);
             }
             L->n_entries++;
-            uint8_t nn[16], m[16];
-            int len;
-            if (!net_number_and_mask(n, nn, &len, m)) return MXP_OK;  // an IPNet that contains nothing
-            if (len == 4) {
-                uint32_t lo = 0, mm = 0;
-                for (int i = 0; i < 4; i++) {
-                    lo = lo << 8 | (uint32_t)(nn[i] & m[i]);
-                    mm = mm << 8 | m[i];
-                }
-                r4.emplace_back(lo, lo | ~mm);
-            } else {
-                unsigned __int128 lo = 0, mm = 0;
-                for (int i = 0; i < 16; i++) {
-                    lo = lo << 8 | (unsigned __int128)(nn[i] & m[i]);
-                    mm = mm << 8 | m[i];
-                }
-                r6.emplace_back(lo, lo | ~mm);
-            }
             return MXP_OK;
         };
         for (uint32_t i = 0; i < n_entries; i++)
             if ((rc = add(str(entries[i], entry_lens[i]), true))) return rc;
         for (uint32_t i = 0; i < n_overrides; i++) add(str(overrides[i], override_lens[i]), false);
-        merge(r4);
-        merge(r6);
+        mxpcidr::merge(r4);
+        mxpcidr::merge(r6);
         std::vector<uint32_t> lo4, hi4;
         std::vector<uint64_t> lo6, hi6;
         for (auto& p : r4) {
@@ -392,13 +286,7 @@ int mxp_list_create(mxp_engine* eng, int entry_type, const char* const* entries,
         }
         L->n4 = (uint32_t)r4.size();
         L->n6 = (uint32_t)r6.size();
-        // /16 directory of the IPv4 intervals: dir[k] = intervals whose start is below k << 16
-        std::vector<uint32_t> dir(65537, 0);
-        for (uint32_t k = 0, i = 0; k <= 65536; k++) {
-            const uint64_t at = (uint64_t)k << 16;
-            while (i < lo4.size() && lo4[i] < at) i++;
-            dir[k] = i;
-        }
+        const std::vector<uint32_t> dir = mxpcidr::v4_directory(lo4);
         if ((rc = put(L->v4dir, dir.data(), dir.size() * 4, "upload v4dir"))) return rc;
         if ((rc = put(L->v4lo, lo4.data(), lo4.size() * 4, "upload v4lo"))) return rc;
         if ((rc = put(L->v4hi, hi4.data(), hi4.size() * 4, "upload v4hi"))) return rc;
