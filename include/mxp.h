@@ -319,6 +319,118 @@ int mxp_listentry_check(mxp_engine* eng, const mxp_list* list, int blacklist, co
                         uint32_t value_rule, int32_t* codes, uint64_t* values);
 
 /*
+ * Batched Check: dispatcher.Check (mixer/pkg/runtime/dispatcher.go:216-236) and combineResults
+ * (dispatcher.go:322-361) for a batch, down to what grpcServer.Check answers with
+ * (mixer/pkg/api/grpcServer.go:160-179): one status code, ValidDuration and ValidUseCount per
+ * request.  The Resolve's action lists stay on the device and are folded there (check.hip).
+ *
+ * A check unit is one (handler, instance) call dispatcher.Check issues for a selected rule:
+ *   MXP_CHECK_UNIT_LIST   a listentry instance (value_rule of the instance engine) against a list
+ *                         handler: list, blacklist, the handler's CachingInterval / CachingUseCount
+ *                         (mixer/adapter/list/list.go:96-100) as valid_duration_ns / valid_use_count;
+ *   MXP_CHECK_UNIT_CONST  a handler that returns a fixed CheckResult whatever the instance (the denier,
+ *                         mixer/adapter/denier/denier.go:60-66): const_code, const_message, the two
+ *                         valid_* numbers.
+ * handler_name is the name combineResults prints (NULL: "").  Rule r's units are
+ * rule_units[rule_unit_off[r] .. rule_unit_off[r + 1]), indices into units, in configuration order.
+ *
+ * Dispatch order: a request's selected rules in resolution order (the order of sel_rules), within a
+ * rule its units in configuration order -- the order dispatch issues the calls in
+ * (dispatcher.go:175-183).  The reference collects results in completion order (dispatcher.go:392-394),
+ * so with more than one worker its "first failure" is whichever call finished first; the issue order
+ * is one of the orders it can produce, and the one this call fixes.
+ *
+ * One unit contributes (list.go:68-101, template.gen.go:2153-2202):
+ *   Value evaluated          the code mxp_list_check defines (0 / 3 / 5 / 7), the unit's two numbers;
+ *   Value's Eval failed      ProcessCheck returns CheckResult{} and an error; the result pointer is
+ *                            non-nil (dispatcher.go:227), so a ZERO result takes part: OK, duration 0,
+ *                            use count 0.  Reported: record code MXP_LISTENTRY_EVAL_ERROR;
+ *   interface Value, not a   the type assertion panics, safeDispatch leaves res == nil and
+ *   string                   combineResults skips it (dispatcher.go:332-334): NO contribution.
+ *                            Reported: record code MXP_LISTENTRY_NOT_STRING;
+ *   const unit               its configured result.
+ * Per request (combineResults, mixer/pkg/adapter/check.go:45-57): valid_duration_ns and
+ * valid_use_count are the signed minima (int64, int32) over the contributed results; code is that of
+ * the first non-OK contributed result in dispatch order, else OK.
+ * The response (grpcServer.go:160-179):
+ *   Resolve error (status[q] != MXP_RESOLVE_OK)   code INTERNAL (13), the plan's defaults (the
+ *       reference's 10 s and 200, grpcServer.go:56-65, given at plan creation), flag
+ *       MXP_CHECK_RESOLVE_ERROR; the text through status / err_rule / mxp_pair_error(rules engine);
+ *   no result contributed (nothing selected, no units, or every unit panicked)   the defaults; code
+ *       OK, or INTERNAL when a unit panicked (err != nil); flag MXP_CHECK_NO_CHECKS;
+ *   otherwise   the combined result.  An Eval error beside a contributed result does NOT change the
+ *       code: its only trace is the 0 / 0 it contributed, and flag MXP_CHECK_EVAL_ERROR.
+ * MXP_CHECK_UNIT_PANIC is set whenever a unit panicked.
+ *
+ * mxp_check_plan_create: `rules` has its resolver set; `instances` is the instance-expression engine
+ * mxp_listentry_check asks for (NULL when every unit is a const unit).  The plan copies units, names
+ * and messages; lists and engines must outlive it.  MXP_ERR_ARG (text: mxp_last_error(rules)) for a
+ * value_rule that does not exist or is not STRING / interface, a unit index out of range, offsets
+ * that do not ascend, engines on different devices.  A rule set compiled (or a resolver set) on either
+ * engine after the plan was created makes mxp_check_batch return MXP_ERR_ARG.
+ *
+ * mxp_check_batch: status / err_rule as mxp_resolve_batch; results[n]; a record for every unit whose
+ * code is not OK (the two negative codes included), in dispatch order: request q's are
+ * recs[rec_off[q] .. rec_off[q + 1]) (rec_off has n + 1 entries), results[q].n_records of them.
+ * record.rule is the selected rule, record.unit the index into units, record.value the Value register
+ * (mxp_value_text on the instance engine) where code > 0, else 0.  MXP_ERR_NOMEM when rec_cap is
+ * short, with status, err_rule, results and rec_off complete (retry with rec_off[n]).  Both engines'
+ * last batch is this one afterwards (mxp_pair_error, mxp_value_text).
+ * MXP_CHECK_GROUP=1|4|16|64 fixes the lanes per request of the fold, MXP_CHECK_IDS32=1 forces u32 ids
+ * on the device (A/B and tests; u16 ids are used up to 65536 rules).
+ *
+ * mxp_check_message: the combineResults text of one request's records (dispatcher.go:344-352): each
+ * record with code > 0 gives "<handler_name>:<message>", joined by ", "; the message is "%s is not
+ * whitelisted" (5), "%s is blacklisted" (7), "%s is not a valid IP address" (3) with the Value's
+ * text, or the const unit's message.  Valid while the batch is the instance engine's last.
+ *
+ * Not covered: referenced attributes of the instance expressions, the multierror text of INTERNAL
+ * responses, Report and Quota dispatch, templates other than listentry and checknothing, device
+ * groups.
+ */
+#define MXP_CHECK_UNIT_LIST 0u
+#define MXP_CHECK_UNIT_CONST 1u
+#define MXP_CHECK_RESOLVE_ERROR 1u
+#define MXP_CHECK_NO_CHECKS 2u
+#define MXP_CHECK_EVAL_ERROR 4u
+#define MXP_CHECK_UNIT_PANIC 8u
+#define MXP_RPC_INTERNAL 13
+typedef struct mxp_check_unit {
+    uint32_t kind;
+    uint32_t value_rule;
+    const mxp_list* list;
+    uint32_t blacklist;
+    int32_t const_code;
+    const char* const_message;
+    int64_t valid_duration_ns;
+    int32_t valid_use_count;
+    const char* handler_name;
+} mxp_check_unit;
+typedef struct mxp_check_result {
+    int64_t valid_duration_ns;
+    int32_t valid_use_count;
+    int32_t code;
+    uint32_t n_records;
+    uint32_t flags;
+} mxp_check_result; /* 24 bytes */
+typedef struct mxp_check_record {
+    uint32_t rule;
+    uint32_t unit;
+    int32_t code;
+    uint32_t pad;
+    uint64_t value;
+} mxp_check_record; /* 24 bytes */
+typedef struct mxp_check_plan mxp_check_plan;
+int mxp_check_plan_create(mxp_engine* rules, mxp_engine* instances, const mxp_check_unit* units, uint32_t n_units,
+                          const uint32_t* rule_unit_off, const uint32_t* rule_units,
+                          int64_t default_valid_duration_ns, int32_t default_valid_use_count, mxp_check_plan** out);
+void mxp_check_plan_destroy(mxp_check_plan* plan);
+int mxp_check_batch(mxp_check_plan* plan, const mxp_bag_batch* batch, uint32_t variety, uint8_t* status,
+                    uint32_t* err_rule, mxp_check_result* results, uint64_t* rec_off, mxp_check_record* recs,
+                    uint64_t rec_cap);
+int mxp_check_message(mxp_check_plan* plan, const mxp_check_record* recs, uint32_t n, char* buf, uint32_t cap);
+
+/*
  * memquota (mixer/adapter/memquota): batched HandleQuota with the reference's sequential semantics.
  *
  * mxp_quota_create: n_keys quota keys with their limit (config.Params_Quota MaxAmount /

@@ -78,6 +78,21 @@ int mxp_resolve_placed(mxp_engine* eng, mxp_dbatch* db, const mxp_bag_batch* bat
                        uint8_t* status, uint32_t* err_rule, uint64_t* sel_off, void* sel_rules,
                        const mxp_resolve_place& place, uint64_t first_cap = 0);
 
+// A Resolve whose ids stay on the device (resolver.cpp; check.cpp folds them there): rule ids as u16
+// (ids16) or u32 in eng->res_sel, their offsets in eng->res_off, *n_ids of them; status and err_rule
+// as mxp_resolve_batch.
+int mxp_resolve_kept(mxp_engine* eng, const mxp_bag_batch* batch, uint32_t variety, bool ids16, uint8_t* status,
+                     uint32_t* err_rule, uint64_t* n_ids);
+// The list kernel's argument block (lists.cpp): the list's own fields for n lookups into d_codes, and
+// for a fused listentry the Value registers of `value_rule` of an evaluation of db on eng (dv the
+// [n][rules] result registers, de the error bitmap; iface: an interface-typed Value).
+struct mxp_list_args;
+struct mxp_list;
+void mxp_list_fill_args(mxp_list_args* A, const mxp_list* L, int blacklist, uint32_t n, int32_t* d_codes);
+void mxp_list_fill_value(mxp_list_args* A, mxp_engine* eng, const mxp_dbatch* db, const uint64_t* dv, const uint32_t* de,
+                         uint32_t value_rule, bool iface);
+int mxp_list_launch(mxp_engine* eng, const mxp_list_args* A, hipStream_t s, const char* what);
+
 // Device blocks of freed batches, reused by later uploads (mxp_batch_free hands a batch's blocks to
 // its engine's bin with events recorded on every stream that read the batch; mxp_batch_upload draws
 // from it).  A hipFree synchronises the whole device -- ~0.2 ms each, ~25 per batch, so freeing one
@@ -831,7 +846,9 @@ struct mxp_engine : public mxp::LowerTables {
         return MXP_ERR_DEVICE;
     }
 
+    uint64_t rules_gen = 0;  // rule sets compiled or dropped so far (a Check plan is made for one: check.cpp)
     void reset_tables() {
+        rules_gen++;
         ret.valid = false;  // (a retained bitmap's record belongs to the old rule set's plans)
         resolver = ResolverConf();  // a new rule set needs a new resolver configuration
         gstr_ids.clear();

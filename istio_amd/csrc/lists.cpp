@@ -206,6 +206,59 @@ void set_lds(mxp_list_args& A, const mxp_list* L) {
 
 }  // namespace
 
+// The list kernel's argument block, shared by mxp_list_check_device, mxp_listentry_check and the
+// batched Check's code planes (check.cpp): the list's fields for n lookups into d_codes ...
+void mxp_list_fill_args(mxp_list_args* out, const mxp_list* L, int blacklist, uint32_t n, int32_t* d_codes) {
+    mxp_list_args& A = *out;
+    memset(&A, 0, sizeof A);
+    A.type = (uint32_t)L->type;
+    A.blacklist = blacklist ? 1u : 0u;
+    A.n = n;
+    A.hmask = L->hmask;
+    A.htab = L->htab.as<uint64_t>();
+    A.ent_desc = L->ent_desc.as<uint64_t>();
+    A.ent_pool = L->ent_pool.as<uint8_t>();
+    A.v4lo = L->v4lo.as<uint32_t>();
+    A.v4hi = L->v4hi.as<uint32_t>();
+    A.v6lo = L->v6lo.as<uint64_t>();
+    A.v6hi = L->v6hi.as<uint64_t>();
+    A.n4 = L->n4;
+    A.n6 = L->n6;
+    A.rx_n = L->rx_n;
+    A.rx_nfa = L->rx_nfa;
+    A.ip_split = ip_split();
+    A.v4dir = L->v4dir.as<uint32_t>();
+    A.opt = list_opt();
+    A.rx = mxp_dfa_set{L->rx_hdr.as<mxp_dfa_hdr>(), L->rx_trans.as<uint32_t>(), L->rx_ascii.as<uint16_t>(),
+                       L->rx_hilo.as<uint32_t>(), L->rx_hicls.as<uint16_t>()};
+    L->nfa_scratch.set(&A.rx);
+    A.codes = d_codes;
+    set_lds(A, L);
+}
+
+// ... and, for a fused listentry, the symbols: the Value registers of rule value_rule (dv: the
+// [n][rules] result registers of an evaluation of db on eng, de its error bitmap)
+void mxp_list_fill_value(mxp_list_args* out, mxp_engine* eng, const mxp_dbatch* db, const uint64_t* dv, const uint32_t* de,
+                         uint32_t value_rule, bool iface) {
+    mxp_list_args& A = *out;
+    const uint32_t NR = (uint32_t)eng->rules.size();
+    A.vals = dv + value_rule;
+    A.vstride = NR;
+    A.viface = iface ? 1u : 0u;
+    A.err_word = de + (size_t)(value_rule / 32) * A.n;
+    A.err_bit = 1u << (value_rule % 32);
+    A.n_gstr = eng->gstrs.size();
+    A.gstr_off = eng->d_gstr_off.as<uint64_t>();
+    A.gstr = eng->d_gstr.as<uint8_t>();
+    A.bstr_off = db->bstr_off.as<uint64_t>();
+    A.bstr = db->bstr.as<uint8_t>();
+}
+
+int mxp_list_launch(mxp_engine* eng, const mxp_list_args* A, hipStream_t s, const char* what) {
+    const hipError_t e = mxp_launch_list(A, s);
+    return e == hipSuccess ? MXP_OK : eng->hipfail(e, what);
+}
+
 extern "C" {
 
 int mxp_list_create(mxp_engine* eng, int entry_type, const char* const* entries, const uint32_t* entry_lens,
@@ -532,34 +585,10 @@ int mxp_list_check_device(mxp_engine* eng, const mxp_list* L, int blacklist, con
     if (!eng || !L || (n && (!d_sym_bytes || !d_sym_offsets || !d_codes))) return MXP_ERR_ARG;
     if (!n) return MXP_OK;
     mxp_list_args A;
-    memset(&A, 0, sizeof A);
-    A.type = (uint32_t)L->type;
-    A.blacklist = blacklist ? 1u : 0u;
-    A.n = n;
-    A.hmask = L->hmask;
+    mxp_list_fill_args(&A, L, blacklist, n, d_codes);
     A.sym = d_sym_bytes;
     A.sym_off = d_sym_offsets;
-    A.htab = L->htab.as<uint64_t>();
-    A.ent_desc = L->ent_desc.as<uint64_t>();
-    A.ent_pool = L->ent_pool.as<uint8_t>();
-    A.v4lo = L->v4lo.as<uint32_t>();
-    A.v4hi = L->v4hi.as<uint32_t>();
-    A.v6lo = L->v6lo.as<uint64_t>();
-    A.v6hi = L->v6hi.as<uint64_t>();
-    A.n4 = L->n4;
-    A.n6 = L->n6;
-    A.rx_n = L->rx_n;
-    A.rx_nfa = L->rx_nfa;
-    A.ip_split = ip_split();
-    A.v4dir = L->v4dir.as<uint32_t>();
-    A.opt = list_opt();
-    A.rx = mxp_dfa_set{L->rx_hdr.as<mxp_dfa_hdr>(), L->rx_trans.as<uint32_t>(), L->rx_ascii.as<uint16_t>(),
-                       L->rx_hilo.as<uint32_t>(), L->rx_hicls.as<uint16_t>()};
-    L->nfa_scratch.set(&A.rx);
-    A.codes = d_codes;
-    set_lds(A, L);
-    hipError_t e = mxp_launch_list(&A, stream ? (hipStream_t)stream : eng->stream);
-    return e == hipSuccess ? MXP_OK : eng->hipfail(e, "launch list check");
+    return mxp_list_launch(eng, &A, stream ? (hipStream_t)stream : eng->stream, "launch list check");
 }
 
 int mxp_listentry_check(mxp_engine* eng, const mxp_list* L, int blacklist, const mxp_bag_batch* batch,
@@ -586,41 +615,9 @@ int mxp_listentry_check(mxp_engine* eng, const mxp_list* L, int blacklist, const
     DevBuf d_codes;
     if ((e = d_codes.alloc((size_t)n * 4)) != hipSuccess) return eng->hipfail(e, "alloc codes");
     mxp_list_args A;
-    memset(&A, 0, sizeof A);
-    A.type = (uint32_t)L->type;
-    A.blacklist = blacklist ? 1u : 0u;
-    A.n = n;
-    A.hmask = L->hmask;
-    A.htab = L->htab.as<uint64_t>();
-    A.ent_desc = L->ent_desc.as<uint64_t>();
-    A.ent_pool = L->ent_pool.as<uint8_t>();
-    A.v4lo = L->v4lo.as<uint32_t>();
-    A.v4hi = L->v4hi.as<uint32_t>();
-    A.v6lo = L->v6lo.as<uint64_t>();
-    A.v6hi = L->v6hi.as<uint64_t>();
-    A.n4 = L->n4;
-    A.n6 = L->n6;
-    A.rx_n = L->rx_n;
-    A.rx_nfa = L->rx_nfa;
-    A.ip_split = ip_split();
-    A.v4dir = L->v4dir.as<uint32_t>();
-    A.opt = list_opt();
-    A.rx = mxp_dfa_set{L->rx_hdr.as<mxp_dfa_hdr>(), L->rx_trans.as<uint32_t>(), L->rx_ascii.as<uint16_t>(),
-                       L->rx_hilo.as<uint32_t>(), L->rx_hicls.as<uint16_t>()};
-    L->nfa_scratch.set(&A.rx);
-    A.codes = d_codes.as<int32_t>();
-    set_lds(A, L);
-    A.vals = dv.as<uint64_t>() + value_rule;
-    A.vstride = NR;
-    A.viface = iface ? 1u : 0u;
-    A.err_word = de.as<uint32_t>() + (size_t)(value_rule / 32) * n;
-    A.err_bit = 1u << (value_rule % 32);
-    A.n_gstr = eng->gstrs.size();
-    A.gstr_off = eng->d_gstr_off.as<uint64_t>();
-    A.gstr = eng->d_gstr.as<uint8_t>();
-    A.bstr_off = db->bstr_off.as<uint64_t>();
-    A.bstr = db->bstr.as<uint8_t>();
-    if ((e = mxp_launch_list(&A, eng->stream)) != hipSuccess) return eng->hipfail(e, "launch listentry");
+    mxp_list_fill_args(&A, L, blacklist, n, d_codes.as<int32_t>());
+    mxp_list_fill_value(&A, eng, db.get(), dv.as<uint64_t>(), de.as<uint32_t>(), value_rule, iface);
+    if ((rc = mxp_list_launch(eng, &A, eng->stream, "launch listentry"))) return rc;
     if ((e = hipMemcpyAsync(codes, d_codes.p, (size_t)n * 4, hipMemcpyDeviceToHost, eng->stream)) != hipSuccess)
         return eng->hipfail(e, "download codes");
     // the Value registers (rule value_rule's column of the [n][NR] result registers), for the

@@ -598,8 +598,11 @@ mxp_engine::Piece offsets_piece(uint64_t* sel_off, const uint64_t* offs, size_t 
 
 // The second phase, stage by stage.  On MXP_ERR_NOMEM status, err_rule and sel_off are complete:
 // every return of it comes after their downloads.
+// kept != nullptr (a batched Check, check.cpp): nothing of the ids is delivered -- the u16 / u32 list
+// stays in res_sel with its offsets in res_off, *kept receives its length, and sel_off / sel_rules
+// are not written.
 int resolve_end(mxp_resolve_job& J, uint8_t* status, uint32_t* err_rule, uint64_t* sel_off, void* sel_rules,
-                uint64_t sel_cap, const mxp_resolve_place* place) {
+                uint64_t sel_cap, const mxp_resolve_place* place, uint64_t* kept = nullptr) {
     mxp_engine* eng = J.eng;
     const uint32_t n = J.n;
     int rc;
@@ -632,12 +635,14 @@ int resolve_end(mxp_resolve_job& J, uint8_t* status, uint32_t* err_rule, uint64_
             (f.encoded && (rc = ids.stream(early_cap, early_cap, group))) || (rc = ids.deliver_early(sel_hd, early_cap)))
             return rc;
     }
+    if (kept) *kept = 0;
     if (!n) {
-        if (!place) sel_off[0] = 0;
+        if (!place && !kept) sel_off[0] = 0;
     } else {
         std::vector<mxp_engine::Piece> outs = {{status, eng->res_status.p, n}, {err_rule, eng->res_err_rule.p, (size_t)n * 4}};
         // (encoded: the byte offsets only where the guarded passes above enqueued them)
-        if (!f.encoded || sel_hd) outs.push_back(offsets_piece(sel_off, ids.offsets(), n, place != nullptr));
+        if (kept) outs.push_back({kept, eng->res_off.as<uint64_t>() + n, 8});
+        else if (!f.encoded || sel_hd) outs.push_back(offsets_piece(sel_off, ids.offsets(), n, place != nullptr));
         if (f.encoded) outs.push_back({&ids.small->ids_total, eng->res_off.as<uint64_t>() + n, 8});
         if ((rc = eng->download_all(outs, "download resolve outputs"))) return rc;
     }
@@ -652,6 +657,7 @@ int resolve_end(mxp_resolve_job& J, uint8_t* status, uint32_t* err_rule, uint64_
         ref_rc = eng->refs_assemble(J.batch, J.recs, &scope, J.ref_off, J.refs, J.ref_cap);
         if (ref_rc && ref_rc != MXP_ERR_NOMEM) return ref_rc;
     }
+    if (kept) return n ? ids.list(*kept, 0, 1u) : MXP_OK;  // (the list written, nothing delivered)
     // encoded, after the first synchronisation: the ids' count is known, and the lanes per request
     // come from the true mean.  The list is written again, and its byte offsets computed and brought
     // back, only if the early list did not fit (or there was none): otherwise both stand.
@@ -714,6 +720,20 @@ int resolve_impl(mxp_engine* eng, const mxp_bag_batch* batch, uint32_t variety, 
 }
 
 }  // namespace
+
+// (check.cpp) a Resolve whose ids stay on the device: rule ids as u16 (ids16) or u32 in res_sel, their
+// offsets in res_off, *n_ids of them; status and err_rule as mxp_resolve_batch
+int mxp_resolve_kept(mxp_engine* eng, const mxp_bag_batch* batch, uint32_t variety, bool ids16, uint8_t* status,
+                     uint32_t* err_rule, uint64_t* n_ids) {
+    if (!eng || !batch || !status || !err_rule || !n_ids || variety >= 32) return MXP_ERR_ARG;
+    mxp_resolve_job J;
+    J.eng = eng;
+    J.batch = batch;
+    J.variety = variety;
+    J.ids = ids16 ? ResIds::U16 : ResIds::U32;
+    if (int rc = resolve_begin(J)) return rc;
+    return resolve_end(J, status, err_rule, nullptr, nullptr, 0, nullptr, n_ids);
+}
 
 int mxp_resolve_placed(mxp_engine* eng, mxp_dbatch* db, const mxp_bag_batch* batch, uint32_t variety, uint32_t flags,
                        uint8_t* status, uint32_t* err_rule, uint64_t* sel_off, void* sel_rules,

@@ -52,6 +52,11 @@ SIGNATURES = {
     "mxp_wire_view": (_VP, [_VP]),
     "mxp_wire_free": (None, [_VP]),
     "mxp_listentry_check": (ctypes.c_int, [_VP, _VP, ctypes.c_int, _VP, ctypes.c_uint32, _VP, _VP]),
+    "mxp_check_plan_create": (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_uint32, _VP, _VP, ctypes.c_int64, ctypes.c_int32,
+                                            ctypes.POINTER(_VP)]),
+    "mxp_check_plan_destroy": (None, [_VP]),
+    "mxp_check_batch": (ctypes.c_int, [_VP, _VP, ctypes.c_uint32, _VP, _VP, _VP, _VP, _VP, ctypes.c_uint64]),
+    "mxp_check_message": (ctypes.c_int, [_VP, _VP, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint32]),
     "mxp_resolve_refs": (ctypes.c_int, [_VP, _VP, ctypes.c_uint32, _VP, _VP, _VP, _VP, ctypes.c_uint64, _VP, _VP,
                                         ctypes.c_uint64]),
     "mxp_eval_values": (ctypes.c_int, [_VP, _VP, _VP, _VP]),
@@ -1079,6 +1084,126 @@ class ListHandle:
             if self.h and not getattr(self, "_view", False):
                 self.eng.lib.mxp_list_destroy(self.eng.h, self.h)
                 self.h = None
+        except Exception:
+            pass
+
+
+# ------------------------------------------------------------------ batched Check (include/mxp.h)
+CHECK_UNIT_LIST, CHECK_UNIT_CONST = 0, 1
+CHECK_RESOLVE_ERROR, CHECK_NO_CHECKS, CHECK_EVAL_ERROR, CHECK_UNIT_PANIC = 1, 2, 4, 8
+RPC_INTERNAL = 13
+LISTENTRY_EVAL_ERROR, LISTENTRY_NOT_STRING = -1, -2
+# mxp_check_result / mxp_check_record, 24 bytes each
+CHECK_RESULT = np.dtype([("valid_duration_ns", "<i8"), ("valid_use_count", "<i4"), ("code", "<i4"),
+                         ("n_records", "<u4"), ("flags", "<u4")])
+CHECK_RECORD = np.dtype([("rule", "<u4"), ("unit", "<u4"), ("code", "<i4"), ("pad", "<u4"), ("value", "<u8")])
+assert CHECK_RESULT.itemsize == 24 and CHECK_RECORD.itemsize == 24
+
+
+class _CheckUnit(ctypes.Structure):  # mxp_check_unit (mxp.h)
+    _fields_ = [("kind", ctypes.c_uint32), ("value_rule", ctypes.c_uint32), ("list", _VP), ("blacklist", ctypes.c_uint32),
+                ("const_code", ctypes.c_int32), ("const_message", ctypes.c_char_p), ("valid_duration_ns", ctypes.c_int64),
+                ("valid_use_count", ctypes.c_int32), ("handler_name", ctypes.c_char_p)]
+
+
+def list_unit(value_rule: int, lst: "ListHandle", blacklist: bool, valid_duration_ns: int, valid_use_count: int,
+              handler_name: str = "") -> dict:
+    """A MXP_CHECK_UNIT_LIST for CheckPlan: a listentry instance against a list handler."""
+    return dict(kind=CHECK_UNIT_LIST, value_rule=value_rule, list=lst, blacklist=bool(blacklist),
+                valid_duration_ns=valid_duration_ns, valid_use_count=valid_use_count, handler_name=handler_name)
+
+
+def const_unit(code: int, message: str, valid_duration_ns: int, valid_use_count: int, handler_name: str = "") -> dict:
+    """A MXP_CHECK_UNIT_CONST for CheckPlan: a handler with a fixed CheckResult (the denier)."""
+    return dict(kind=CHECK_UNIT_CONST, const_code=code, const_message=message, valid_duration_ns=valid_duration_ns,
+                valid_use_count=valid_use_count, handler_name=handler_name)
+
+
+class CheckPlan:
+    """mxp_check_plan: dispatcher.Check + combineResults for batches.  `rules` has its resolver set,
+    `instances` holds the listentry Value expressions (None when every unit is a const unit); units:
+    list_unit / const_unit dicts; rule_units[r]: the unit indices of rule r, in configuration order.
+    The defaults are grpcServer.go's 10 s and 200."""
+
+    def __init__(self, rules: Engine, instances: Optional[Engine], units, rule_units,
+                 default_valid_duration_ns: int = 10 * 10 ** 9, default_valid_use_count: int = 200,
+                 rule_unit_off=None):
+        self.rules, self.instances, self.units = rules, instances, list(units)
+        self.lib = rules.lib
+        cu = (_CheckUnit * max(len(self.units), 1))()
+        self._keep = []
+        for i, u in enumerate(self.units):
+            cu[i].kind = u["kind"]
+            cu[i].value_rule = u.get("value_rule", 0)
+            lst = u.get("list")
+            cu[i].list = lst.h if lst is not None else None
+            cu[i].blacklist = int(u.get("blacklist", False))
+            cu[i].const_code = u.get("const_code", 0)
+            cu[i].const_message = u.get("const_message", "").encode()
+            cu[i].valid_duration_ns = u["valid_duration_ns"]
+            cu[i].valid_use_count = u["valid_use_count"]
+            cu[i].handler_name = u.get("handler_name", "").encode()
+            self._keep.append(lst)
+        if rule_unit_off is None:  # rule_units: one sequence per rule
+            off = np.zeros(len(rule_units) + 1, dtype=np.uint32)
+            off[1:] = np.cumsum([len(x) for x in rule_units]) if len(rule_units) else []
+            flat = np.array([u for x in rule_units for u in x] or [0], dtype=np.uint32)
+        else:                      # (the C arrays as given)
+            off = np.ascontiguousarray(rule_unit_off, dtype=np.uint32)
+            flat = np.ascontiguousarray(list(rule_units) or [0], dtype=np.uint32)
+        self.h = _VP()
+        rules._check(self.lib.mxp_check_plan_create(rules.h, instances.h if instances is not None else None, cu,
+                                                    len(self.units), off.ctypes.data, flat.ctypes.data,
+                                                    default_valid_duration_ns, default_valid_use_count,
+                                                    ctypes.byref(self.h)), "mxp_check_plan_create")
+
+    def check_raw(self, batch: BagBatch, variety: int, cap: int):
+        """mxp_check_batch as called -> (rc, status, err_rule, results, rec_off, recs[cap])."""
+        n = batch.n
+        status, err_rule = np.zeros(n, np.uint8), np.zeros(n, np.uint32)
+        results, rec_off = np.zeros(n, CHECK_RESULT), np.zeros(n + 1, np.uint64)
+        recs = np.zeros(max(cap, 1), CHECK_RECORD)
+        rc = self.lib.mxp_check_batch(self.h, ctypes.byref(batch.c_struct()), variety, status.ctypes.data,
+                                      err_rule.ctypes.data, results.ctypes.data, rec_off.ctypes.data,
+                                      recs.ctypes.data if cap else None, cap)
+        return rc, status, err_rule, results, rec_off, recs
+
+    def check(self, batch: BagBatch, variety: int, cap: int = 0):
+        """-> (status u8[n], err_rule u32[n], results CHECK_RESULT[n], rec_off u64[n + 1], recs
+        CHECK_RECORD[rec_off[n]]): request q's records are recs[rec_off[q]:rec_off[q + 1]].  Retries
+        once with the exact size when the record capacity is short (MXP_ERR_NOMEM)."""
+        cap = cap or max(16, batch.n // 4)
+        for _ in range(2):
+            rc, status, err_rule, results, rec_off, recs = self.check_raw(batch, variety, cap)
+            if rc == 4:
+                cap = int(rec_off[batch.n])
+                continue
+            break
+        self.rules._check(rc, "mxp_check_batch")
+        return status, err_rule, results, rec_off, recs[:int(rec_off[batch.n])]
+
+    def message(self, records) -> str:
+        """mxp_check_message: the combineResults text of one request's records (valid while the batch
+        is the instance engine's last)."""
+        recs = np.ascontiguousarray(records, dtype=CHECK_RECORD)
+        cap = 1 << 12
+        while True:
+            buf = ctypes.create_string_buffer(cap)
+            rc = self.lib.mxp_check_message(self.h, recs.ctypes.data if len(recs) else None, len(recs), buf, cap)
+            if rc == 4:
+                cap *= 4
+                continue
+            self.rules._check(rc, "mxp_check_message")
+            return buf.value.decode("utf-8", "surrogateescape")
+
+    def close(self):
+        if self.h:
+            self.lib.mxp_check_plan_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 
