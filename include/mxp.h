@@ -385,8 +385,8 @@ int mxp_listentry_check(mxp_engine* eng, const mxp_list* list, int blacklist, co
  * text, or the const unit's message.  Valid while the batch is the instance engine's last.
  *
  * Not covered: referenced attributes of the instance expressions, the multierror text of INTERNAL
- * responses, Report and Quota dispatch, templates other than listentry and checknothing, device
- * groups.
+ * responses, Report dispatch (Quota dispatch: mxp_quota_batch, below), templates other than
+ * listentry and checknothing, device groups.
  */
 #define MXP_CHECK_UNIT_LIST 0u
 #define MXP_CHECK_UNIT_CONST 1u
@@ -504,6 +504,125 @@ int mxp_quota_alloc_dedup_device(mxp_engine* eng, mxp_quota* quota, uint32_t n, 
                                  int64_t* d_granted, int64_t* d_valid_ns, uint8_t* d_dup, int64_t* d_delta);
 int mxp_quota_dedup_reap(mxp_engine* eng, mxp_quota* quota, void* stream);
 int mxp_quota_dedup_stats(mxp_engine* eng, mxp_quota* quota, uint64_t out[4]);
+
+/*
+ * Batched Quota: dispatcher.Quota (mixer/pkg/runtime/dispatcher.go:242-281, :160-187), the quota
+ * template's instance (template.gen.go:2807-2849) and memquota's HandleQuota with its limit() and
+ * makeKey() (memquota.go:65-116, keys.go:35-95) down to CheckResponse.Quotas[name]
+ * (mixer/pkg/api/grpcServer.go:188-257), with no per-request host work.  One plan is one memquota
+ * handler: one key space, one dedup state.
+ *
+ * `rules` is an engine with a resolver set, `instances` an engine of its own whose rules are the
+ * dimension expressions (a unit's value_rules), evaluated in Eval mode.  limits: config.Params_Quota
+ * by name, each with its overrides in configuration order; units: the quota instances
+ * (instance_name = a limit's name; at most 32 dimensions, labels distinct).  rule_unit[r]: a unit
+ * index, MXP_QUOTA_NO_UNIT (rule r has no quota action: the walk goes on) or MXP_QUOTA_OTHER_UNIT
+ * (the rule dispatches to another handler: the walk stops, the request is not this plan's).
+ *
+ * Per request, in this order: skip[q] != 0 -> SKIPPED (a caller passes the requests whose Check code
+ * was not OK); a Resolve error -> RESOLVE_ERROR (INTERNAL); the first selected rule with a unit, in
+ * resolution order, dispatches that unit and nothing else (the quota name in the request is ignored,
+ * as in the reference); none -> NOT_APPLIED: granted = the amount asked, valid_ns = the default.
+ * The unit's dimensions are the instance engine's result registers: a failed Eval -> EVAL_ERROR with
+ * `failed` = the mask of the failing labels by their index in the unit (their texts: mxp_pair_error
+ * on the instance engine); HandleQuota is then never called.  Otherwise limit() picks the first
+ * override whose every configured dimension equals the instance's value -- a STRING equal to the
+ * configured string; an int64, float64, bool or []byte value never matches, nor does a label the
+ * instance lacks; an override without dimensions matches everything -- else the quota's own numbers.
+ * Amount 0 returns QuotaResult{}: OK, granted 0, no key made, no state touched.  Else the key text is
+ * makeKey's: the name, then per label in sort.Strings order ';' label '=' value, a string as its
+ * bytes, an int64 / float64 / bool as 32 NUL bytes followed by strconv's AppendInt(v, 16) /
+ * AppendFloat(v, 'b', -1, 64) / AppendBool (keys.go appends to bytes[:] of a [32]byte).
+ *
+ * Dimension values: STRING, INT64, DOUBLE and BOOL expressions, and interface-typed expressions
+ * whose run-time kind is STRING, BOOL or BYTES ([]byte: IP addresses, ip() results; the bytes are
+ * written as they are, and never match an override).  Refused, never approximated: an expression of
+ * static type DURATION fails plan creation (MXP_ERR_ARG, the message names the unit and the label);
+ * an interface value of any other run-time kind gives that request KEY_UNSUPPORTED: DURATION,
+ * TIMESTAMP and STRING_MAP (formatted by String() / per pair in the reference), and an INT64 or
+ * DOUBLE held by an interface-typed expression -- an attribute declared IP_ADDRESS, TIMESTAMP or
+ * STRING_MAP that holds a number -- because the engine's interface registers keep 56 bits of it.
+ *
+ * Classes and ids: a class is a (limit, default) or (limit, override) pair; every key of a class has
+ * the same MaxAmount and ValidDuration, and class c owns the ids [base_c, base_c + key_cap_c), in
+ * the order limits and their overrides are given.  The plan's mxp_quota has sum(key_cap) keys.
+ * Within a call the new keys of a class take the class's next free ids in order of their first
+ * arrival index; ids persist across calls, so they are a function of the call sequence alone.  Every
+ * request that reaches HandleQuota with amount != 0 interns its key, a dedup hit or not.  A class
+ * without an id left: KEYS_FULL for the key's requests, granted 0, nothing touched; the call returns
+ * MXP_ERR_NOMEM (mxp_last_error says so) after answering every request.  The key text is not injective (labels a, b:
+ * a = "x;b=y", b = "z" and a = "x", b = "y;b=z" print the same bytes, and may match different
+ * overrides; the reference then runs one cell under two limits): the table stores the class, and a
+ * text held -- or first seen in this call -- under another class is KEY_CONFLICT.
+ *
+ * mxp_quota_batch: amount / best_effort per request; id_bytes / id_off (u32[n + 1]) the
+ * DeduplicationIDs as for mxp_quota_alloc_dedup, or both NULL for no deduplication; skip nullable;
+ * status / err_rule as mxp_resolve_batch.  OK answers carry granted / valid_ns / dup as
+ * mxp_quota_alloc_dedup defines them.  The plan is stale once either engine compiles again (MXP_ERR_ARG).
+ * mxp_quota_plan_eval + mxp_quota_keys_device: the key stage alone.  The first evaluates the
+ * instance engine on a batch; the second takes device arrays of n = that batch's requests -- a unit
+ * per request (MXP_QUOTA_NO_UNIT: none, NOT_APPLIED) and the amounts -- and writes key ids, codes
+ * (int32) and the full failed masks, enqueued on `stream` after one synchronisation of it.
+ * mxp_quota_key_text: the bytes of an interned id (they may hold NULs), two small copies from the
+ * device behind the rules engine's stream; *len is set even when cap is short (MXP_ERR_NOMEM).
+ * mxp_quota_plan_stats: out = {keys held, table slots, pool bytes, classes,
+ * then the keys held per class, cap - 4 of them at most}; synchronises.
+ * MXP_QKEY_HASH_BITS (environment, at plan creation) masks the key hash, as MXP_QDD_HASH_BITS.
+ *
+ * Not covered: device groups (mxp_group_quota_* take key ids), referenced attributes of the
+ * dimension expressions, the multierror text, batches uploaded ahead, Report.
+ */
+#define MXP_QUOTA_NO_UNIT 0xFFFFFFFFu
+#define MXP_QUOTA_OTHER_UNIT 0xFFFFFFFEu
+#define MXP_QUOTA_OK 0
+#define MXP_QUOTA_NOT_APPLIED 1
+#define MXP_QUOTA_OTHER 2
+#define MXP_QUOTA_SKIPPED 3
+#define MXP_QUOTA_RESOLVE_ERROR 4
+#define MXP_QUOTA_EVAL_ERROR (-1)
+#define MXP_QUOTA_KEY_UNSUPPORTED (-2)
+#define MXP_QUOTA_KEYS_FULL (-3)
+#define MXP_QUOTA_KEY_CONFLICT (-4)
+typedef struct mxp_quota_override {
+    const char* const* labels;
+    const char* const* values;
+    uint32_t n;
+    int64_t max_amount, valid_duration_ns;
+    uint32_t key_cap;
+} mxp_quota_override;
+typedef struct mxp_quota_limit {
+    const char* name;
+    int64_t max_amount, valid_duration_ns;
+    uint32_t key_cap;
+    const mxp_quota_override* overrides;
+    uint32_t n_overrides;
+} mxp_quota_limit;
+typedef struct mxp_quota_unit {
+    const char* instance_name; /* = a limit's name */
+    const char* const* labels;
+    const uint32_t* value_rules;
+    uint32_t n_dims;
+} mxp_quota_unit;
+typedef struct mxp_quota_answer {
+    int64_t granted, valid_ns;
+    uint32_t key; /* ~0: none */
+    int16_t code;
+    uint8_t dup, failed;
+} mxp_quota_answer; /* 24 bytes */
+typedef struct mxp_quota_plan mxp_quota_plan;
+int mxp_quota_plan_create(mxp_engine* rules, mxp_engine* instances, const mxp_quota_limit* limits, uint32_t n_limits,
+                          const mxp_quota_unit* units, uint32_t n_units, const uint32_t* rule_unit,
+                          int64_t default_valid_duration_ns, mxp_quota_plan** out);
+void mxp_quota_plan_destroy(mxp_quota_plan* plan);
+mxp_quota* mxp_quota_plan_quota(mxp_quota_plan* plan);
+int mxp_quota_batch(mxp_quota_plan* plan, const mxp_bag_batch* batch, uint32_t variety, const int64_t* amount,
+                    const uint8_t* best_effort, const uint8_t* id_bytes, const uint32_t* id_off, const uint8_t* skip,
+                    int64_t now_ns, uint8_t* status, uint32_t* err_rule, mxp_quota_answer* out);
+int mxp_quota_plan_eval(mxp_quota_plan* plan, const mxp_bag_batch* batch);
+int mxp_quota_keys_device(mxp_quota_plan* plan, uint32_t n, const uint32_t* d_unit, const int64_t* d_amount, void* stream,
+                          uint32_t* d_key, int32_t* d_code, uint32_t* d_failed);
+int mxp_quota_key_text(mxp_quota_plan* plan, uint32_t key_id, uint8_t* buf, uint32_t cap, uint32_t* len);
+int mxp_quota_plan_stats(mxp_quota_plan* plan, uint64_t* out, uint32_t cap);
 
 /*
  * Regex compiler check (host only; test and tooling hook): compiles `pattern` with the engine's Go

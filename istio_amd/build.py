@@ -18,8 +18,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = os.environ.get("MXP_OFFLOAD_ARCH", "gfx950")
 
 SOURCES = ["goutil.cpp", "frontend.cpp", "ilgen.cpp", "lower.cpp", "vmopt.cpp", "regex.cpp", "engine.cpp",
-           "resolver.cpp", "refs.cpp", "wire.cpp", "lists.cpp", "quota.cpp", "quota_dedup.cpp", "pack_device.cpp", "debug.cpp", "kernels.hip", "resolve.hip", "lists.hip", "quota.hip", "quota_dedup.hip", "pack.hip", "group.cpp", "group.hip", "delta8.hip", "check.cpp", "check.hip"]
-HEADERS = ["goutil.h", "frontend.h", "ilgen.h", "lower.h", "vmopt.h", "vm.h", "kargs.h", "engine_impl.h", "resolve_args.h", "delta8_args.h", "check_args.h", "netparse.h", "cidr.h", "timeparse.h", "lists.h", "regex.h", "unicode_tables.h", "dfa_dev.h", "quota_args.h", "quota_impl.h", "quota_dedup_args.h", "pack_args.h", "par.h", "goupper.h", "upper_table.h"]
+           "resolver.cpp", "refs.cpp", "wire.cpp", "lists.cpp", "quota.cpp", "quota_dedup.cpp", "pack_device.cpp", "debug.cpp", "kernels.hip", "resolve.hip", "lists.hip", "quota.hip", "quota_dedup.hip", "pack.hip", "group.cpp", "group.hip", "delta8.hip", "check.cpp", "check.hip", "quota_keys.cpp", "quota_keys.hip"]
+HEADERS = ["goutil.h", "frontend.h", "ilgen.h", "lower.h", "vmopt.h", "vm.h", "kargs.h", "engine_impl.h", "resolve_args.h", "delta8_args.h", "check_args.h", "netparse.h", "cidr.h", "timeparse.h", "lists.h", "regex.h", "unicode_tables.h", "dfa_dev.h", "quota_args.h", "quota_impl.h", "quota_dedup_args.h", "quota_bytes.h", "quota_keys_args.h", "quota_key_fmt.h", "pack_args.h", "par.h", "goupper.h", "upper_table.h"]
 
 
 def _stale():

@@ -106,6 +106,15 @@ SIGNATURES = {
                                                     ctypes.c_uint32, ctypes.c_int64, _VP, _VP, _VP, _VP, _VP]),
     "mxp_quota_dedup_reap": (ctypes.c_int, [_VP, _VP, _VP]),
     "mxp_quota_dedup_stats": (ctypes.c_int, [_VP, _VP, _VP]),
+    "mxp_quota_plan_create": (ctypes.c_int, [_VP, _VP, _VP, ctypes.c_uint32, _VP, ctypes.c_uint32, _VP, ctypes.c_int64,
+                                            ctypes.POINTER(_VP)]),
+    "mxp_quota_plan_destroy": (None, [_VP]),
+    "mxp_quota_plan_quota": (_VP, [_VP]),
+    "mxp_quota_batch": (ctypes.c_int, [_VP, _VP, ctypes.c_uint32, _VP, _VP, _VP, _VP, _VP, ctypes.c_int64, _VP, _VP, _VP]),
+    "mxp_quota_plan_eval": (ctypes.c_int, [_VP, _VP]),
+    "mxp_quota_keys_device": (ctypes.c_int, [_VP, ctypes.c_uint32, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "mxp_quota_key_text": (ctypes.c_int, [_VP, ctypes.c_uint32, _VP, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32)]),
+    "mxp_quota_plan_stats": (ctypes.c_int, [_VP, _VP, ctypes.c_uint32]),
     "mxp_batch_eval_device_hits": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "mxp_batch_eval_device_compact": (ctypes.c_int, [_VP, _VP, _VP, _VP, _VP, _VP]),
     "mxp_set_timing": (ctypes.c_int, [_VP, ctypes.c_int]),
@@ -1287,6 +1296,161 @@ class QuotaHandle:
             if self.h:
                 self.eng.lib.mxp_quota_destroy(self.eng.h, self.h)
                 self.h = None
+        except Exception:
+            pass
+
+
+# mxp_quota_batch (mxp.h): codes, rule_unit specials, the 24-byte answer
+QUOTA_OK, QUOTA_NOT_APPLIED, QUOTA_OTHER, QUOTA_SKIPPED, QUOTA_RESOLVE_ERROR = 0, 1, 2, 3, 4
+QUOTA_EVAL_ERROR, QUOTA_KEY_UNSUPPORTED, QUOTA_KEYS_FULL, QUOTA_KEY_CONFLICT = -1, -2, -3, -4
+QUOTA_NO_UNIT, QUOTA_OTHER_UNIT, QUOTA_NO_KEY = 0xFFFFFFFF, 0xFFFFFFFE, 0xFFFFFFFF
+QUOTA_ANSWER = np.dtype([("granted", "<i8"), ("valid_ns", "<i8"), ("key", "<u4"), ("code", "<i2"), ("dup", "u1"),
+                         ("failed", "u1")])
+assert QUOTA_ANSWER.itemsize == 24
+
+
+class _QuotaOverride(ctypes.Structure):  # mxp_quota_override (mxp.h)
+    _fields_ = [("labels", ctypes.POINTER(ctypes.c_char_p)), ("values", ctypes.POINTER(ctypes.c_char_p)),
+                ("n", ctypes.c_uint32), ("max_amount", ctypes.c_int64), ("valid_duration_ns", ctypes.c_int64),
+                ("key_cap", ctypes.c_uint32)]
+
+
+class _QuotaLimit(ctypes.Structure):  # mxp_quota_limit
+    _fields_ = [("name", ctypes.c_char_p), ("max_amount", ctypes.c_int64), ("valid_duration_ns", ctypes.c_int64),
+                ("key_cap", ctypes.c_uint32), ("overrides", ctypes.POINTER(_QuotaOverride)), ("n_overrides", ctypes.c_uint32)]
+
+
+class _QuotaUnit(ctypes.Structure):  # mxp_quota_unit
+    _fields_ = [("instance_name", ctypes.c_char_p), ("labels", ctypes.POINTER(ctypes.c_char_p)),
+                ("value_rules", ctypes.POINTER(ctypes.c_uint32)), ("n_dims", ctypes.c_uint32)]
+
+
+def _cstrs(strs):
+    arr = (ctypes.c_char_p * max(len(strs), 1))()
+    for i, s in enumerate(strs):
+        arr[i] = s.encode("utf-8", "surrogateescape") if isinstance(s, str) else bytes(s)
+    return arr
+
+
+class QuotaPlan:
+    """mxp_quota_plan: dispatcher.Quota, the quota instance and memquota's HandleQuota for batches.
+    limits: [{"name", "max_amount", "valid_duration_ns", "key_cap", "overrides": [{"dimensions": {label:
+    value}, "max_amount", "valid_duration_ns", "key_cap"}]}]; units: [{"instance_name", "labels",
+    "value_rules"}] (value_rules: rules of `instances`); rule_unit[r]: a unit index, QUOTA_NO_UNIT or
+    QUOTA_OTHER_UNIT.  The default duration is grpcServer.go's 10 s."""
+
+    def __init__(self, rules: Engine, instances: Optional[Engine], limits, units, rule_unit,
+                 default_valid_duration_ns: int = 10 * 10 ** 9):
+        self.rules, self.instances, self.lib = rules, instances, rules.lib
+        keep = []
+        cl = (_QuotaLimit * max(len(limits), 1))()
+        for i, lim in enumerate(limits):
+            ovs = lim.get("overrides", ())
+            co = (_QuotaOverride * max(len(ovs), 1))()
+            for j, o in enumerate(ovs):
+                dims = o.get("dimensions", {})
+                labels, values = _cstrs(list(dims.keys())), _cstrs(list(dims.values()))
+                keep += [labels, values]
+                co[j].labels, co[j].values, co[j].n = labels, values, len(dims)
+                co[j].max_amount, co[j].valid_duration_ns, co[j].key_cap = o["max_amount"], o["valid_duration_ns"], o["key_cap"]
+            keep.append(co)
+            cl[i].name = lim["name"].encode()
+            cl[i].max_amount, cl[i].valid_duration_ns, cl[i].key_cap = lim["max_amount"], lim["valid_duration_ns"], lim["key_cap"]
+            cl[i].overrides, cl[i].n_overrides = co, len(ovs)
+        cu = (_QuotaUnit * max(len(units), 1))()
+        for i, u in enumerate(units):
+            labels = _cstrs(u["labels"])
+            vr = (ctypes.c_uint32 * max(len(u["labels"]), 1))(*u["value_rules"])
+            keep += [labels, vr]
+            cu[i].instance_name = u["instance_name"].encode()
+            cu[i].labels, cu[i].value_rules, cu[i].n_dims = labels, vr, len(u["labels"])
+        ru = np.ascontiguousarray(list(rule_unit) or [0], dtype=np.uint32)
+        self.h = _VP()
+        rules._check(self.lib.mxp_quota_plan_create(rules.h, instances.h if instances is not None else None, cl, len(limits),
+                                                    cu, len(units), ru.ctypes.data, default_valid_duration_ns,
+                                                    ctypes.byref(self.h)), "mxp_quota_plan_create")
+
+    def quota_handle(self) -> int:
+        """mxp_quota_plan_quota: the plan's mxp_quota (owned by the plan), for the plain calls."""
+        return self.lib.mxp_quota_plan_quota(self.h)
+
+    def reap(self, stream=0):
+        """mxp_quota_dedup_reap on the plan's quota."""
+        self.rules._check(self.lib.mxp_quota_dedup_reap(self.rules.h, self.quota_handle(), stream or None),
+                          "mxp_quota_dedup_reap")
+
+    @staticmethod
+    def pack_ids(ids):
+        """One DeduplicationID (bytes) per request -> (blob u8, offsets u32[n + 1]) as mxp_quota_batch takes them."""
+        off = np.zeros(len(ids) + 1, dtype=np.uint32)
+        off[1:] = np.cumsum(np.fromiter((len(i) for i in ids), dtype=np.int64, count=len(ids)))
+        return np.frombuffer(b"".join(ids) + b"\0", dtype=np.uint8), off  # (never empty)
+
+    def batch_raw(self, batch: BagBatch, variety: int, amounts, best_effort, now_ns: int, ids=None, skip=None):
+        """mxp_quota_batch as called -> (rc, status, err_rule, answers QUOTA_ANSWER[n]).  ids: one
+        DeduplicationID (bytes) per request or pack_ids' pair, or None for no deduplication."""
+        n = batch.n
+        a = np.ascontiguousarray(amounts, dtype=np.int64)
+        b = np.ascontiguousarray(best_effort, dtype=np.uint8)
+        status, err_rule, out = np.zeros(n, np.uint8), np.zeros(n, np.uint32), np.zeros(n, QUOTA_ANSWER)
+        blob = off = sk = None
+        if ids is not None:
+            blob, off = ids if isinstance(ids, tuple) else self.pack_ids(ids)
+        if skip is not None:
+            sk = np.ascontiguousarray(skip, dtype=np.uint8)
+        rc = self.lib.mxp_quota_batch(self.h, ctypes.byref(batch.c_struct()), variety, a.ctypes.data if n else None,
+                                      b.ctypes.data if n else None, blob.ctypes.data if blob is not None else None,
+                                      off.ctypes.data if off is not None else None,
+                                      sk.ctypes.data if sk is not None and n else None, int(now_ns),
+                                      status.ctypes.data if n else None, err_rule.ctypes.data if n else None,
+                                      out.ctypes.data if n else None)
+        return rc, status, err_rule, out
+
+    def batch(self, batch: BagBatch, variety: int, amounts, best_effort, now_ns: int, ids=None, skip=None):
+        """-> (status, err_rule, answers).  A class that ran out of key ids (MXP_ERR_NOMEM) still answers
+        every request: the answers are returned, their KEYS_FULL codes tell, and `keys_full` is set."""
+        rc, status, err_rule, out = self.batch_raw(batch, variety, amounts, best_effort, now_ns, ids, skip)
+        self.keys_full = rc == 4
+        if rc != 4:
+            self.rules._check(rc, "mxp_quota_batch")
+        return status, err_rule, out
+
+    def eval(self, batch: BagBatch):
+        """mxp_quota_plan_eval: the dimension values of `batch`, for keys_device."""
+        self.rules._check(self.lib.mxp_quota_plan_eval(self.h, ctypes.byref(batch.c_struct())), "mxp_quota_plan_eval")
+
+    def keys_device(self, n, d_unit, d_amount, stream, d_key, d_code, d_failed):
+        """mxp_quota_keys_device: device pointers (u32 units, i64 amounts -> u32 keys, i32 codes, u32 masks)."""
+        self.rules._check(self.lib.mxp_quota_keys_device(self.h, n, d_unit, d_amount, stream or None, d_key, d_code,
+                                                         d_failed), "mxp_quota_keys_device")
+
+    def key_text(self, key_id: int) -> bytes:
+        n = ctypes.c_uint32(0)
+        cap = 256
+        while True:
+            buf = (ctypes.c_uint8 * cap)()
+            rc = self.lib.mxp_quota_key_text(self.h, key_id, buf, cap, ctypes.byref(n))
+            if rc == 4:
+                cap = n.value
+                continue
+            self.rules._check(rc, "mxp_quota_key_text")
+            return bytes(buf[:n.value])
+
+    def stats(self) -> dict:
+        out = np.zeros(4 + 256, dtype=np.uint64)
+        self.rules._check(self.lib.mxp_quota_plan_stats(self.h, out.ctypes.data, len(out)), "mxp_quota_plan_stats")
+        c = int(out[3])
+        return dict(keys=int(out[0]), table_slots=int(out[1]), pool_bytes=int(out[2]), classes=c,
+                    class_keys=[int(v) for v in out[4:4 + c]])
+
+    def close(self):
+        if self.h:
+            self.lib.mxp_quota_plan_destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
         except Exception:
             pass
 

@@ -711,6 +711,58 @@ def quota_workload(n_keys=1024, n_requests=1_000_000, seed=5, p_free=0.1, p_zero
     return out + (idx,) if return_index else out
 
 
+QUOTA_VARIETY = 2  # istio.mixer.adapter.model.v1beta1.TemplateVariety: CHECK 0, REPORT 1, QUOTA 2
+QUOTA_DIM_ATTRS = ("source.user", "source.namespace", "api.operation", "api.version")
+
+
+def quota_instance_workload(n_rules=1000, n_requests=1_000_000, n_keys=1024, seed=6):
+    """The Quota path end to end (engine.QuotaPlan): C2 rules and requests in one namespace; every
+    fourth rule carries a quota action (the QUOTA variety bit, unit 0), the rest only CHECK.  One unit,
+    instance `requestcount`, with four STRING dimensions over attributes of the C2 manifest, drawn so
+    that the requests name n_keys distinct keys with Zipf(1.05) popularity (quota_key_weights); one
+    override, on source.namespace == "ns1" (keys 32 .. 63 of every 256: a tenth of the requests).  Amounts, best effort and frees as quota_workload; one
+    DeduplicationID per request, 2 % repeating an earlier one.
+    Returns dict(manifest, rules, conf, batch, inst_rules, limits, units, rule_unit, amounts,
+    best_effort, ids, key_index)."""
+    manifest, rules, b = c2_workload(n_rules=n_rules, n_requests=n_requests, seed=seed)
+    rng = np.random.default_rng(seed + 500)
+    n = b.n
+    k = rng.choice(n_keys, size=n, p=quota_key_weights(n_keys))
+    strings = [b.string(i) for i in range(b.n_strings)]
+    parts = [(32, b"user%d"), (8, b"ns%d"), (4, b"op%d"), ((n_keys + 1023) // 1024, b"v%d")]
+    cols = {name: (kk, vv) for name, kk, vv in zip(b.names, b.kinds, b.values)}
+    div = 1
+    for name, (m, fmt) in zip(QUOTA_DIM_ATTRS, parts):
+        base = len(strings)
+        strings += [fmt % i for i in range(m)]
+        cols[name] = (np.full(n, STRING, dtype=np.uint8), (base + (k // div) % m).astype(np.uint64))
+        div *= m
+    batch = BagBatch.from_columns(n, cols, strings)
+    has_quota = np.arange(n_rules) % 4 == 0
+    conf = dict(rule_ns=["istio-system"] * n_rules,
+                variety_mask=[(1 | (1 << QUOTA_VARIETY)) if q else 1 for q in has_quota],
+                is_tcp=[0] * n_rules, empty_match=[0] * n_rules,
+                identity_attr="destination.service", default_ns="istio-system")
+    limits = [{"name": "requestcount", "max_amount": 5000, "valid_duration_ns": 10**9, "key_cap": 2 * n_keys,
+               "overrides": [{"dimensions": {"sourcens": "ns1"}, "max_amount": 50, "valid_duration_ns": 10**9,
+                              "key_cap": n_keys}]}]
+    units = [{"instance_name": "requestcount", "labels": ["sourceuser", "sourcens", "operation", "version"],
+              "value_rules": [0, 1, 2, 3]}]
+    amounts = rng.integers(1, 21, size=n).astype(np.int64)
+    r = rng.random(n)
+    amounts = np.where(r < 0.1, -amounts, amounts)
+    amounts = np.where(r > 0.98, 0, amounts)
+    be = (rng.random(n) < 0.5).astype(np.uint8)
+    src = np.arange(n)
+    rep = np.nonzero(rng.random(n) < 0.02)[0]
+    rep = rep[rep > 0]
+    src[rep] = (rng.random(len(rep)) * rep).astype(np.int64)
+    ids = [b"req-%08d" % i for i in src.tolist()]
+    return dict(manifest=manifest, rules=rules, conf=conf, batch=batch, inst_rules=list(QUOTA_DIM_ATTRS), limits=limits,
+                units=units, rule_unit=[0 if q else 0xFFFFFFFF for q in has_quota], amounts=amounts, best_effort=be,
+                ids=ids, key_index=k)
+
+
 # pieces of case-insensitive list symbols beyond ASCII (Go 1.9 strings.ToUpper, goupper.h): case
 # pairs, runes with no simple uppercase (ß, ŉ, Georgian in 9.0), runes whose capital is ASCII (ı, ſ),
 # titlecase digraphs, Greek with iota subscripts, astral scripts, and invalid UTF-8 bytes
