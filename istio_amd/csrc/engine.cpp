@@ -577,7 +577,7 @@ int mxp_engine::build_plan(Plan& P) {
                 rule_tmpl2[i] = it->second;
             }
             comp_of[{gd.col, sa.col}][{k1, sa.k2}].push_back(i);
-            if (base) ref_comp.push_back(RefComposite{gd.col & 0xFFFFFFu, sa.col, (uint32_t)k1, i});
+            if (base) ref_comp.push_back(RefComposite{gd.col & 0xFFFFFFu, sa.col, i, gd.col >> 24, k1});
             P.n_composite++;
             continue;
         }

@@ -534,8 +534,10 @@ struct mxp_engine : public mxp::LowerTables {
     static constexpr size_t kDenseMin = 8;
     DevBuf d_dense_cm;  // [n] per-request dense masks of the current evaluation
     // referenced attributes (mxp_eval_refs, refs.cpp)
-    struct RefComposite {
-        uint32_t a_col, b_col, k1, rule;  // `A == K1 && B.startsWith(K2) ...`: B is read iff A == K1
+    struct RefComposite {  // `A == K1 && B.startsWith(K2) ...`: B is read iff A == K1
+        uint32_t a_col, b_col, rule;
+        uint32_t kind;  // A's want class (W_*) or GK_VCOL: the request kinds that pass, and what K1 is
+        uint64_t k1;    // a string id (W_S, GK_VCOL) or the 64-bit value compared against
     };
     std::vector<RefComposite> ref_comp;
     std::vector<uint32_t> ref_guard;               // [rule] column its guard reads (MXP_VM_DONE: none)

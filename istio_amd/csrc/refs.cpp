@@ -6,7 +6,9 @@
 //   * the guard column of a guarded rule (its program starts by reading it: vmopt.h) -- the guard
 //     and index phases decide such pairs without running the VM;
 //   * for composite-indexed rules `A == K1 && B.startsWith(K2) && ...` (vmopt.h SecondAtom), B when
-//     A holds the string K1 (the second atom runs exactly then);
+//     A holds K1 (the second atom runs exactly then): A's kind passes the guard's want class and its
+//     value is the string K1 (a string column, or a map[key] virtual column of a present map: "" when
+//     the map lacks the key) or the 64-bit pattern K1 (INT64 / DURATION, DOUBLE, BOOL);
 //   * every read the VM performs for the pairs it runs (continuations, unguarded rules), recorded by
 //     the *_refs kernels (kernels.hip ref_rec) as (request, rule, column | map lookup).
 // Conditions follow from the bag: absent -> ABSENCE, present -> EXACT, a string map fetched whole ->
@@ -101,27 +103,31 @@ int mxp_engine::refs_assemble(const mxp_bag_batch* b, const std::vector<mxp_ref_
         const int64_t vp = vocab_find(b->column_names[c]);
         if (vp >= 0) battr[c] = (uint32_t)vp;
     }
-    // the rules of each composite (A, B) pair with their K1 strings (aliases included)
+    // the rules of each composite (A, its guard kind, B) with their K1 (aliases included): a string
+    // for string and map[key] guards, else the 64-bit value
     struct CompRule {
         uint32_t rule;
-        std::string_view k1;
+        std::string_view s;
+        uint64_t v;
     };
     struct CompGroup {
-        uint32_t a, b;
+        uint32_t a, b, kind;
         std::vector<CompRule> rules;
+        bool text() const { return kind == W_S || kind == GK_VCOL; }
     };
     std::vector<CompGroup> comps;
     for (const RefComposite& x : ref_comp) {
         CompGroup* g = nullptr;
         for (auto& y : comps)
-            if (y.a == x.a_col && y.b == x.b_col) g = &y;
+            if (y.a == x.a_col && y.b == x.b_col && y.kind == x.kind) g = &y;
         if (!g) {
-            comps.push_back(CompGroup{x.a_col, x.b_col, {}});
+            comps.push_back(CompGroup{x.a_col, x.b_col, x.kind, {}});
             g = &comps.back();
         }
-        g->rules.push_back(CompRule{x.rule, std::string_view(gstrs[x.k1])});
+        const CompRule cr{x.rule, g->text() ? std::string_view(gstrs[(uint32_t)x.k1]) : std::string_view(), x.k1};
+        g->rules.push_back(cr);
         for (uint32_t j = ref_alias_off[x.rule]; j < ref_alias_off[x.rule + 1]; j++)
-            g->rules.push_back(CompRule{ref_aliases[j], std::string_view(gstrs[x.k1])});
+            g->rules.push_back(CompRule{ref_aliases[j], cr.s, cr.v});
     }
     // Rule lists a request evaluates, each with the set of rules of the list it may evaluate: all
     // rules (no scope), or per (namespace, tcp) the resolver-eligible ones.  Per list: the first rule
@@ -130,7 +136,8 @@ int mxp_engine::refs_assemble(const mxp_bag_batch* b, const std::vector<mxp_ref_
     struct RuleList {
         uint32_t lo = 0, hi = 0;
         std::vector<std::pair<uint32_t, uint32_t>> guard_first;  // (column, first rule)
-        std::vector<std::unordered_map<std::string_view, uint32_t, mxp::SvHash>> comp_first;  // [group]
+        std::vector<std::unordered_map<std::string_view, uint32_t, mxp::SvHash>> comp_first;  // [group], by string
+        std::vector<std::unordered_map<uint64_t, uint32_t>> comp_first_v;                    // [group], by value
     };
     const bool scoped = scope != nullptr;
     const auto& RC = resolver;
@@ -148,11 +155,13 @@ int mxp_engine::refs_assemble(const mxp_bag_batch* b, const std::vector<mxp_ref_
         }
         L.guard_first.assign(first.begin(), first.end());
         L.comp_first.resize(comps.size());
+        L.comp_first_v.resize(comps.size());
         for (size_t g = 0; g < comps.size(); g++)
             for (const CompRule& cr : comps[g].rules) {
                 if (cr.rule < lo || cr.rule >= hi || (tcp >= 0 && !eligible(cr.rule, (uint32_t)tcp))) continue;
-                auto ins = L.comp_first[g].emplace(cr.k1, cr.rule);
-                if (!ins.second && cr.rule < ins.first->second) ins.first->second = cr.rule;
+                uint32_t* first = comps[g].text() ? &L.comp_first[g].emplace(cr.s, cr.rule).first->second
+                                                  : &L.comp_first_v[g].emplace(cr.v, cr.rule).first->second;
+                if (cr.rule < *first) *first = cr.rule;
             }
         return L;
     };
@@ -196,11 +205,12 @@ int mxp_engine::refs_assemble(const mxp_bag_batch* b, const std::vector<mxp_ref_
         return std::string_view((const char*)b->str_bytes + b->str_offsets[sid],
                                 (size_t)(b->str_offsets[sid + 1] - b->str_offsets[sid]));
     };
-    auto map_has = [&](uint64_t m, std::string_view key) {
+    auto map_find = [&](uint64_t m, std::string_view key) -> int64_t {  // the entry of `key`, or -1
         for (uint64_t x = b->map_offsets[m]; x < b->map_offsets[m + 1]; x++)
-            if (bstr(b->map_keys[x]) == key) return true;
-        return false;
+            if (bstr(b->map_keys[x]) == key) return (int64_t)x;
+        return -1;
     };
+    auto map_has = [&](uint64_t m, std::string_view key) { return map_find(m, key) >= 0; };
     std::vector<uint32_t> count(n, 0);
     const unsigned T = mxp::pack_threads();
     std::vector<std::vector<mxp_attr_ref>> part(T);
@@ -260,10 +270,28 @@ int mxp_engine::refs_assemble(const mxp_bag_batch* b, const std::vector<mxp_ref_
                 for (const auto& gf : act[i]->guard_first)
                     if (gf.second <= cut[i]) add_slot(gf.first);
                 for (size_t g = 0; g < comps.size(); g++) {
-                    const int32_t ca = bc[comps[g].a];
-                    if (ca < 0 || b->kinds[ca][q] != MXP_STRING) continue;
-                    auto it = act[i]->comp_first[g].find(bstr(b->values[ca][q]));
-                    if (it != act[i]->comp_first[g].end() && it->second <= cut[i]) add_slot(comps[g].b);
+                    // the first rule of the list whose K1 is the request's A, if A passes the guard
+                    const CompGroup& G = comps[g];
+                    const int32_t ca = bc[G.a];
+                    if (ca < 0) continue;
+                    const uint32_t ka = b->kinds[ca][q];
+                    const uint64_t va = b->values[ca][q];
+                    uint32_t first = MXP_VM_DONE;
+                    if (G.kind == GK_VCOL) {  // map[key] of a present map: the key's value, "" without the key
+                        if (ka != MXP_STRING_MAP || G.a < C) continue;
+                        const int64_t x = map_find(va, vcols[G.a - C].second);
+                        auto it = act[i]->comp_first[g].find(x < 0 ? std::string_view() : bstr(b->map_values[x]));
+                        if (it != act[i]->comp_first[g].end()) first = it->second;
+                    } else if (!((okset_of(G.kind) >> ka) & 1u)) {
+                        continue;
+                    } else if (G.kind == W_S) {
+                        auto it = act[i]->comp_first[g].find(bstr(va));
+                        if (it != act[i]->comp_first[g].end()) first = it->second;
+                    } else {
+                        auto it = act[i]->comp_first_v[g].find(va);
+                        if (it != act[i]->comp_first_v[g].end()) first = it->second;
+                    }
+                    if (first != MXP_VM_DONE && first <= cut[i]) add_slot(G.b);
                 }
             }
             // does the request evaluate rule r (or one of its duplicates, whose reads are the same)?
